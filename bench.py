@@ -9,6 +9,12 @@ sequence length 2048, on N MI355X of one node (BASELINE.json configs[1] / config
 
 Synthetic (image, chosen, rejected) triples and HF-default random-init weights (no datasets/checkpoints
 exist offline); inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  ``--full`` adds everything else the benchmark
+measures: the per-kernel GEMM / attention table (``roofline``, event timers around every launch of the timed steps), the
+single-GPU data-parallel probe, the N-GPU self-diagnosis (``dp_diag``) and the CPU baseline.  ``--dump-outputs DIR``
+writes what the last timed step computed (loss, log-probs, DPO terms, grad norm, seeded samples of the updated weights
+and of the gradient) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -193,7 +199,7 @@ def cpu_baseline(seed: int = 0, pairs: int = 4, text_len: int = 512):
     (tools/cpu_reference_baseline.py -> profiles/r02_cpu_reference_baseline.json), ride along as ``reference_run``."""
     from oracle import dpo_oracle as O
     cores = os.cpu_count() or 1
-    threads = min(cores, 128)
+    threads = min(torch.get_num_threads(), 128)     # the process's thread budget (OMP_NUM_THREADS, else the physical cores)
     torch.set_num_threads(threads)
     res = {}
     D0, D1 = 2, 4               # round 6 (VERDICT r5 next 7): depths 2 and 4 - the 1 -> 2 slope of round 5 carried depth 1's cache-warm
@@ -248,6 +254,32 @@ def cpu_baseline(seed: int = 0, pairs: int = 4, text_len: int = 512):
     except Exception:
         pass
     return out
+
+
+DUMP_SAMPLE = 1 << 21          # elements per sampled flat buffer: 3 x 8 MB of float32
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir: str, loss, model, trainer) -> None:
+    """What the last timed step handed its caller, as float32 .npy files under ``out_dir``: the loss, the DPO terms and
+    log-probs of the forward, the clip statistics, and a fixed seeded sample (same indices in every run of the same
+    workload) of the updated trainable weights (bf16 and fp32 master) and of the step's gradient."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    out, st = model.last_out, model.store
+    arrays = {"loss": loss.detach().reshape(1), "dpo_scalars": out.scalars, "dpo_per_pair": out.per_pair,
+              "seq_logp": out.seq_logp, "seq_cnt": out.seq_cnt, "per_token_logp": out.per_token_logp,
+              "grad_clip": trainer._clip}
+    n = st.n_train
+    idx = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+    idx = idx.to(st.flat_g.device)
+    arrays["params_sample"] = st.train_p[idx]
+    arrays["grad_sample"] = st.flat_g[idx]
+    if st.flat_master is not None and st.flat_master.numel() == n:      # (ZeRO-1 keeps only this rank's shard)
+        arrays["master_sample"] = st.flat_master[idx]
+    for name, t in arrays.items():
+        if t is not None:
+            np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def _free_port() -> int:
@@ -306,13 +338,22 @@ def main():
     ap.add_argument("--no-dp-diag", action="store_true",
                     help="N > 1: skip the self-diagnosis after the timed region (RCCL rank / channel account, per-bucket enqueue -> "
                          "complete timeline, and 3 extra steps each in RV_ALLREDUCE_MODE overlap / serial / skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: GEMM / attention event timers in the timed steps (roofline), "
+                         "the single-GPU data-parallel probe, the N-GPU self-diagnosis and the CPU baseline (each still "
+                         "switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, < 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    gemm_timer_on = args.full and not args.no_gemm_timer
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))                 # no launcher: spawn one rank per GPU ourselves
     from rlaif_v_amd.dist import init_process_group_from_env, BucketedAllReduce, make_reducer
     rccl_log = None
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not args.no_dp_diag:
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1 and args.full and not args.no_dp_diag:
         # RCCL's own account of what it built (ranks, channels, transport) per rank -> parsed into dp_diag below
         rccl_log = os.path.join(REPO, "gpurun_out", "rccl_bench_rank%s.log" % os.environ.get("RANK", "0"))
         os.makedirs(os.path.dirname(rccl_log), exist_ok=True)
@@ -379,7 +420,7 @@ def main():
     for _ in range(args.warmup):
         one_step()
     timer = GemmTimer()
-    if not args.no_gemm_timer:
+    if gemm_timer_on:
         if getattr(model, "last_out", None) is not None:
             GemmTimer.set_attention_plan(model.last_out.plan)      # the batch (hence the plan) is the same in every step
         timer.install()
@@ -403,12 +444,14 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if args.dump_outputs and rank == 0:      # before the --full probes below run further steps
+        dump_outputs(args.dump_outputs, loss, model, trainer)
 
     dp_diag = None
     zero1 = getattr(reducer, "sharded", False)
-    if world > 1 and zero1:
+    if world > 1 and args.full and zero1:
         dp_diag = dict(skipped="RV_ZERO1=1: the three-mode re-timing swaps in the replicated reducer, whose optimizer state this run freed")
-    if world > 1 and not args.no_dp_diag and not zero1:
+    if world > 1 and args.full and not args.no_dp_diag and not zero1:
         # The first N-GPU run explains itself: nothing below touches the timed region above.
         #   * the same step re-timed (median of 3, max over ranks) with the gradient exchange overlapped (the default), SERIALISED on
         #     the compute stream, and SKIPPED: exposed communication = overlap - skip, what overlap buys = serial - overlap;
@@ -432,7 +475,7 @@ def main():
                 tt = torch.tensor(per, dtype=torch.float64, device=dev)
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
                 return sorted(tt.tolist())[1], [round(x, 1) for x in tt.tolist()], tl
-            if not args.no_gemm_timer:
+            if gemm_timer_on:
                 timer._restore()
             dp_diag = dict(world=world, grad_bytes_per_step=int(model.store.flat_g.numel() * model.store.flat_g.element_size()))
             for mode in ("overlap", "serial", "skip"):        # skip LAST: it leaves the replicas with different weights
@@ -455,7 +498,7 @@ def main():
             dp_diag = dict(error=repr(e)[:300])
 
     dp_probe = None
-    if world == 1 and not args.no_dp_probe:
+    if world == 1 and args.full and not args.no_dp_probe:
         # The data-parallel exchange priced on ONE GPU.  No xGMI peer exists here and a 1-rank RCCL all-reduce never launches
         # a device kernel, so the communication side is played by a REAL concurrent kernel: at every on_bucket_ready of the
         # N-GPU schedule (same bucket merging, same 13.5 GB per step) `n_wg` persistent workgroups on a side stream stream
@@ -491,7 +534,7 @@ def main():
                     done, self.launched = self.launched, []
                     return done
 
-            if not args.no_gemm_timer:
+            if gemm_timer_on:
                 timer._restore()
 
             def timed_steps(n=3):
@@ -605,7 +648,7 @@ def main():
             line["vision_tower"] = dict(kind="EVA02-E/14 (timm eva02_enormous_patch14_clip_224, last block dropped), frozen, forward only",
                                         params=tower.n_params(), flops_per_image=vis_tower, blocks=tower.cfg.blocks_used,
                                         tokens_per_image=(cfg.image_size // tower.cfg.patch) ** 2, parity="unpinned (timm absent offline)")
-        if not args.no_gemm_timer:
+        if gemm_timer_on:
             g = timer.summary()
             traffic, traffic_file = None, None
             # the committed PMC passes were collected on THE HEADLINE CONFIG (full fine-tune, 32 layers, L = 2048, 8 pairs, one GPU):
@@ -681,7 +724,7 @@ def main():
             line["dp_standin_probe_1gpu"] = dp_probe
         if dp_diag is not None:
             line["dp_diag"] = dp_diag
-        if world == 1 and not args.no_cpu_baseline and not args.lora and not args.omnilmm and not args.ragged:     # the CPU leg times the full-FT oracle step
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.lora and not args.omnilmm and not args.ragged:     # the CPU leg times the full-FT oracle step
             line["cpu_baseline"] = cpu_baseline()
     if world > 1:
         dist.barrier()

@@ -638,3 +638,37 @@ def test_lora_and_skinny_dispatch_conditions(monkeypatch):
     assert fwd(256, 512, 4096, 2048) == ["rv_gemm_nt_lora_bf16"]
     monkeypatch.setenv("RV_LORA_FWD_PRE", "1")
     assert fwd(3072, 512, 4096, 2048) == ["rv_gemm_nn_lora_pre_bf16"]
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on host stand-ins of the model state: float32 .npy files, the same seeded sample indices in every
+    run, well under 64 MB, and no master sample when the fp32 master is only this rank's shard (ZeRO-1)."""
+    import numpy as np
+    from types import SimpleNamespace as NS
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0")         # bench.py sets it at import; undone after the test
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n, t0 = 5_000_000, 1000
+    flat_p = torch.arange(t0 + n, dtype=torch.float32).bfloat16()
+    st = NS(n_train=n, flat_p=flat_p, train_p=flat_p[t0:], flat_g=torch.randn(n).bfloat16(), flat_master=torch.arange(n, dtype=torch.float32))
+    out = NS(scalars=torch.randn(8), per_pair=torch.randn(5, 4), seq_logp=torch.randn(8), seq_cnt=torch.arange(8), per_token_logp=torch.randn(300))
+    model, trainer = NS(last_out=out, store=st), NS(_clip=torch.tensor([3.0, 0.5]))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(0.25), model, trainer)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(f + ".npy" for f in ("loss", "dpo_scalars", "dpo_per_pair", "seq_logp", "seq_cnt", "per_token_logp",
+                                                "grad_clip", "params_sample", "grad_sample", "master_sample"))
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        total += os.path.getsize(tmp_path / "a" / f)
+    assert total < 64 * 2**20
+    m = np.load(tmp_path / "a" / "master_sample.npy")
+    assert m.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(m) >= 0) and m.max() < n
+    assert np.array_equal(np.load(tmp_path / "a" / "params_sample.npy"), torch.from_numpy(m + t0).bfloat16().float().numpy())
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == 0.25
+    st.flat_master = torch.zeros(n // 8)                           # ZeRO-1 shard
+    bench.dump_outputs(str(tmp_path / "c"), torch.tensor(0.25), model, trainer)
+    assert "master_sample.npy" not in os.listdir(tmp_path / "c")

@@ -1,5 +1,5 @@
 """Does the data-parallel stand-in kernel really run BESIDE the backward GEMMs?  Reads a rocprofv3 --kernel-trace rocpd
-database of `bench.py --dp-probe-only` and reports, for every reduce_copy_persistent_kernel launch, how much of its interval
+database of `bench.py --full --no-cpu-baseline --dp-probe-wgs 8` and reports, for every reduce_copy_persistent_kernel launch, how much of its interval
 is covered by other kernels (and by which).  Usage: python tools/dp_overlap_from_trace.py results.db [out.json]"""
 import json
 import re

@@ -9,8 +9,8 @@
 #   cfg45         full-depth config 4 / 5 parity (tests/test_zzz_configs45_full_depth_gpu.py)
 #   gputests      the whole GPU tier (pytest -m gpu), as the driver runs it
 #   yardstick     tools/yardstick_hipblaslt.py
-#   bench         default bench.py line (headline config)
-#   benchfast     headline config without the CPU baseline / DP probe
+#   bench         bench.py --full line (headline config + roofline, DP probe, CPU baseline)
+#   benchfast     bench.py --full without the CPU baseline / DP probe (keeps the roofline table)
 #   ragged        bench.py --ragged, pad-free vs rectangular
 #   lora          bench.py --lora --seq-len 4096 --pairs-per-gpu 4
 #   omnilmm       bench.py --omnilmm (config 4 from pixels)
@@ -34,11 +34,11 @@ for st in "$@"; do
     cfg45)     timeout 2400 python -m pytest tests/test_zzz_configs45_full_depth_gpu.py -q -s 2>&1 | tail -60 | tee $OUT/pytest_cfg45.log ;;
     gputests)  timeout 3000 python -m pytest tests -q -m gpu 2>&1 | tail -40 | tee $OUT/pytest_gpu.log ;;
     yardstick) timeout 600 python tools/yardstick_hipblaslt.py 2>&1 | tee $OUT/yardstick_hipblaslt.log | tail -40 ;;
-    bench)     timeout 900 python bench.py > $OUT/bench_line.json 2> $OUT/bench_err.log; tail -c 1500 $OUT/bench_line.json ;;
-    benchfast) timeout 600 python bench.py --no-cpu-baseline --no-dp-probe > $OUT/bench_line_fast.json 2> $OUT/bench_fast_err.log; head -c 600 $OUT/bench_line_fast.json; echo ;;
-    ragged)    for pf in 1 0; do RV_PAD_FREE=$pf timeout 600 python bench.py --ragged --pairs-per-gpu ${RV_RAGGED_PAIRS:-12} --no-dp-probe --steps 4 > $OUT/bench_line_ragged_padfree$pf.json 2> $OUT/bench_ragged_err$pf.log; head -c 500 $OUT/bench_line_ragged_padfree$pf.json; echo; done ;;
-    lora)      timeout 600 python bench.py --lora --seq-len 4096 --pairs-per-gpu 4 --no-dp-probe > $OUT/bench_line_lora.json 2> $OUT/bench_lora_err.log; head -c 600 $OUT/bench_line_lora.json; echo ;;
-    omnilmm)   timeout 900 python bench.py --omnilmm --no-dp-probe > $OUT/bench_line_omnilmm_pixels.json 2> $OUT/bench_omnilmm_err.log; head -c 600 $OUT/bench_line_omnilmm_pixels.json; echo ;;
+    bench)     timeout 900 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_err.log; tail -c 1500 $OUT/bench_line.json ;;
+    benchfast) timeout 600 python bench.py --full --no-cpu-baseline --no-dp-probe > $OUT/bench_line_fast.json 2> $OUT/bench_fast_err.log; head -c 600 $OUT/bench_line_fast.json; echo ;;
+    ragged)    for pf in 1 0; do RV_PAD_FREE=$pf timeout 600 python bench.py --full --ragged --pairs-per-gpu ${RV_RAGGED_PAIRS:-12} --no-dp-probe --steps 4 > $OUT/bench_line_ragged_padfree$pf.json 2> $OUT/bench_ragged_err$pf.log; head -c 500 $OUT/bench_line_ragged_padfree$pf.json; echo; done ;;
+    lora)      timeout 600 python bench.py --full --lora --seq-len 4096 --pairs-per-gpu 4 --no-dp-probe > $OUT/bench_line_lora.json 2> $OUT/bench_lora_err.log; head -c 600 $OUT/bench_line_lora.json; echo ;;
+    omnilmm)   timeout 900 python bench.py --full --omnilmm --no-dp-probe > $OUT/bench_line_omnilmm_pixels.json 2> $OUT/bench_omnilmm_err.log; head -c 600 $OUT/bench_line_omnilmm_pixels.json; echo ;;
     prof)      bash tools/profile_bench.sh $R/bench_kernel python $PWD/bench.py --steps 3 --no-cpu-baseline --no-dp-probe --no-gemm-timer; head -25 gpurun_out/$R/bench_kernel_stats.csv ;;
     pmc)       bash tools/collect_pmc_traffic.sh > $OUT/pmc_collect.log 2>&1; cp gpurun_out/pmc_hbm_traffic.json $OUT/pmc_hbm_traffic.json; tail -c 400 $OUT/pmc_hbm_traffic.json; echo ;;
     pmcattn)   bash tools/pmc_attn_r04.sh $R 2>&1 | tail -4; cp gpurun_out/pmc_attn_$R.txt $OUT/pmc_attn.txt ;;
