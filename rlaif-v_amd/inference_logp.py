@@ -2,7 +2,7 @@
 
 Mirrors /root/reference muffin/eval/muffin_inference_logp.py:
   InferenceSampler                 :55-79    contiguous rank shards
-  get_multimodal_sample_logps      :213-281  (is_llava15 branch) -> forward-only reuse of the training kernels
+  get_multimodal_sample_logps      :213-281  (both branches) -> forward-only reuse of the training kernels
   write_logp_to_preference_parquet :283-313  same `logps` JSON column, 5000-row parquet chunks
   inference_logp                   :315-344
 Differences that do not change the stored values: any batch size is accepted (the reference is pinned to 1,
@@ -76,9 +76,13 @@ class PreferenceInferenceDataset(torch.utils.data.Dataset):
 
 def get_multimodal_sample_logps(model, dataloader, tokenizer=None, is_llava15: bool = True):
     """Returns (win_logp, win_avg_logp, win_per_token_logp, rej_logp, rej_avg_logp, rej_per_token_logp) as Python
-    lists, one entry per sample; per-token lists have spliced_length - 1 entries like the reference's."""
-    if not is_llava15:
-        raise NotImplementedError("only the LLaVA-1.5 branch is implemented")
+    lists, one entry per sample; per-token lists have spliced_length - 1 entries like the reference's.
+    ``is_llava15=False`` is the generic branch (:253-261, ``model(input_ids, labels, images)``) for a model whose splice keeps
+    the text positions (OmniLMM): the same all-rows forward, and the per-token lists then have T - 1 entries, aligned with
+    the collator's token weights."""
+    if not is_llava15 and not getattr(model, "splice_keeps_positions", False):
+        raise ValueError("is_llava15=False (the generic precompute branch) needs a model whose image splice keeps the text "
+                         "positions (OmniLMM)")
     # results stay on the DEVICE while the loop runs (a few KB per row) and come back once at the end: a .tolist() per batch and
     # branch stalls the stream 2 x 83 k times on the full RLAIF-V set
     parts = {k: ([], [], []) for k in ("win", "rej")}

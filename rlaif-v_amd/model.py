@@ -672,6 +672,12 @@ class LlavaDPOModel:
         """Row-level splice rule handed to the planners (None = LLaVA's expanding <image> splice, splice._splice_rows)."""
         return None
 
+    @property
+    def splice_keeps_positions(self) -> bool:
+        """True when the image splice leaves every text token at its position (OmniLMM replaces the <im_patch> embeddings in
+        place): the precondition of the generic get_beta_and_logps branch and of token-weighted DPO."""
+        return bool(getattr(self._row_splicer(), "keeps_positions", False))
+
     # ------------------------------------------------------------------ decoder projections (+ LoRA)
     def _lora_grouping(self, grp: str) -> Tuple[int, int]:
         """(group_cols, group0) of the fused LoRA GEMM for a fused projection (rv_gemm_nt_lora_bf16)."""
@@ -902,12 +908,16 @@ class LlavaDPOModel:
 
     # ------------------------------------------------------------------ forward
     def forward_logps(self, input_ids: torch.Tensor, labels: torch.Tensor, images: torch.Tensor,
-                      save_for_backward: bool = True, all_rows: bool = False, label_shift: int = 1) -> StepOutput:
+                      save_for_backward: bool = True, all_rows: bool = False, label_shift: int = 1,
+                      token_weight: Optional[torch.Tensor] = None) -> StepOutput:
         """Everything of get_beta_and_logps up to ``get_batch_logps``: returns per-sequence log-prob sums
         and counts (muffin/eval/muffin_inference_logp.py:82-115) without materialising logits.
         ``all_rows`` (forward only, reference layout): evaluate EVERY position like
         ``get_batch_logps(return_all=True)`` does - masked positions get the log-prob of token id 0, exactly what
-        the reference stores in its ``logps`` parquet column."""
+        the reference stores in its ``logps`` parquet column.
+        ``token_weight`` [2B, T-1] (token-weighted DPO, position-keeping splices only): the plan gathers it onto the selected
+        rows, ``seq_logp`` / ``seq_cnt`` become the weighted sum and the weighted count (compute_weighted_logp,
+        trainers.py:128-137) and backward scales each row's coefficient by its weight."""
         cfg, st = self.cfg, self.store
         d, H, hd, f = cfg.hidden, cfg.heads, cfg.head_dim, cfg.ffn
         B = len(images)                  # tensor [B, 3, H, W] or a list of raw uint8 [H, W, 3] images
@@ -919,6 +929,8 @@ class LlavaDPOModel:
         if all_rows:
             if save_for_backward:
                 raise ValueError("all_rows is a forward-only mode")
+            if token_weight is not None:
+                raise ValueError("all_rows returns per-token log-probs; token weights apply to the selected-row step")
             plan = build_splice_plan(input_ids, labels, cfg.n_image_tokens, B, cfg.model_max_length, splicer=self._row_splicer())
             nxt = plan.labels[:, 1:]
             S_, Lm1 = nxt.shape
@@ -931,13 +943,16 @@ class LlavaDPOModel:
         elif label_shift != 1:
             # get_batch_logps_minicpm convention (labels pre-shifted, muffin_inference_logp.py:21-52): reference layout only
             plan = build_splice_plan(input_ids, labels, cfg.n_image_tokens, B, cfg.model_max_length, label_shift=label_shift,
-                                     splicer=self._row_splicer())
+                                     splicer=self._row_splicer(), token_weight=token_weight)
         elif self.share_prefix and input_ids.shape[0] == 2 * B:
             plan = build_packed_plan(input_ids, labels, cfg.n_image_tokens, B, cfg.model_max_length, cfg.pad_token_id,
-                                     splicer=self._row_splicer(), pad_free=self.pad_free)
+                                     splicer=self._row_splicer(), pad_free=self.pad_free, token_weight=token_weight)
         else:
-            plan = build_splice_plan(input_ids, labels, cfg.n_image_tokens, B, cfg.model_max_length, splicer=self._row_splicer())
+            plan = build_splice_plan(input_ids, labels, cfg.n_image_tokens, B, cfg.model_max_length, splicer=self._row_splicer(),
+                                     token_weight=token_weight)
         plan = plan.to(self.device)
+        if token_weight is not None:
+            w_rows = plan.w_sel          # [n_sel] fp32: rv_seq_sum weighs the sums / counts, rv_row_coef the row coefficients
         S, L = plan.S, plan.L
         N = plan.n_tokens                # S * L in the rectangular layouts, the sum of the packed rows' lengths when pad-free
         feats = self.encode_images(images, ctx if save_for_backward else None)

@@ -54,6 +54,7 @@ class SplicePlan:
     row_off: Optional[torch.Tensor] = None    # int32 [S] PAD-FREE packed layout: first token row of packed row s (None: s * L)
     row_len: Optional[torch.Tensor] = None    # int32 [S] ... and its length; L is then the LONGEST row (grid / lse stride / RoPE table)
     n_tokens: int = 0                         # rows of the token-major activation buffers (S * L when rectangular)
+    w_sel: Optional[torch.Tensor] = None      # fp32 [n_sel] token weight of each selected row (token-weighted DPO), else None
 
     def to(self, device) -> "SplicePlan":
         kw = {}
@@ -102,6 +103,28 @@ def _splice_rows(input_ids: torch.Tensor, labels: torch.Tensor, n_img_tokens: in
     return rows_src, rows_lab
 
 
+def _check_token_weight(token_weight: Optional[torch.Tensor], splicer, n_seq: int) -> Optional[torch.Tensor]:
+    """The collator's ``token_weight [n_seq, T-1]`` (column t weighs the row that predicts label t+1) as fp32 on the CPU.
+    Token weights index TEXT positions, so they only apply to a splice that keeps every token at its position (OmniLMM's
+    in-place replacement); a length-changing splice (LLaVA-1.5) raises like the reference (trainers.py:246-248)."""
+    if token_weight is None:
+        return None
+    if not getattr(splicer, "keeps_positions", False):
+        raise NotImplementedError("token-weighted DPO needs a splice that keeps text positions (OmniLMM): the LLaVA-1.5 splice "
+                                  "changes the sequence length, so the text-length token weights do not line up with its "
+                                  "rows (the reference raises here too, muffin/train/trainers.py:246-248)")
+    token_weight = token_weight.detach().cpu().to(torch.float32)
+    if token_weight.dim() != 2 or token_weight.shape[0] != n_seq:
+        raise ValueError(f"token_weight must be [{n_seq}, T-1], got {tuple(token_weight.shape)}")
+    return token_weight
+
+
+def _gather_weight(token_weight: torch.Tensor, s: int, cols: torch.Tensor) -> torch.Tensor:
+    if cols.numel() and int(cols.max()) >= token_weight.shape[1]:
+        raise ValueError(f"token_weight has {token_weight.shape[1]} columns, sequence {s} selects column {int(cols.max())}")
+    return token_weight[s, cols]
+
+
 def make_omnilmm_splicer(im_patch: int, im_start: int, im_end: int):
     """Row splicer for the OmniLMM convention (omnilmm/model/omnilmm.py:221-257, use_im_start_end): the ``num_query``
     <im_patch> embeddings behind an <im_start> are REPLACED by the image's resampler features - no length change, labels
@@ -130,6 +153,7 @@ def make_omnilmm_splicer(im_patch: int, im_start: int, im_end: int):
             rows_src.append(src)
             rows_lab.append(lab.clone())
         return rows_src, rows_lab
+    splicer.keeps_positions = True          # row position = text position: token weights apply (build_*_plan token_weight)
     return splicer
 
 
@@ -166,13 +190,19 @@ def _tables(flat: torch.Tensor, n_feat_rows: int):
 
 
 def build_splice_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_tokens: int, n_images: int,
-                      max_len: Optional[int], label_shift: int = 1, splicer=None) -> SplicePlan:
+                      max_len: Optional[int], label_shift: int = 1, splicer=None,
+                      token_weight: Optional[torch.Tensor] = None) -> SplicePlan:
     """Reference layout.  input_ids/labels: int64 [S, T] (the collator's ``concatenated_*`` tensors);
     ``n_images`` distinct images were encoded (one per pair).  label_shift = 1: get_batch_logps
     (labels[:, 1:] vs logits[:, :-1], muffin_inference_logp.py:93-94); 0: get_batch_logps_minicpm (labels already
-    shifted by the data pipeline: labels[:, :-1] vs logits[:, :-1], :32-33)."""
+    shifted by the data pipeline: labels[:, :-1] vs logits[:, :-1], :32-33).
+    ``token_weight`` [S, T-1] (token-weighted DPO, position-keeping splicers only): selected row (s, t) takes
+    token_weight[s, t]; returned in selection order as ``w_sel``."""
     if label_shift not in (0, 1):
         raise ValueError("label_shift must be 0 (minicpm) or 1 (llava / omnilmm)")
+    token_weight = _check_token_weight(token_weight, splicer, input_ids.shape[0])
+    if token_weight is not None and label_shift != 1:
+        raise NotImplementedError("token weights under the minicpm label convention (label_shift=0)")
     input_ids = input_ids.cpu().long()
     labels = labels.cpu().long()
     S = input_ids.shape[0]
@@ -194,16 +224,23 @@ def build_splice_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_token
     seq_off = torch.zeros(S + 1, dtype=torch.int32)
     seq_off[1:] = torch.cumsum(mask.sum(1), 0).to(torch.int32)
 
+    w_sel = None
+    if token_weight is not None:
+        if l_idx.numel() and int(l_idx.max()) >= token_weight.shape[1]:
+            raise ValueError(f"token_weight has {token_weight.shape[1]} columns, a target sits at column {int(l_idx.max())}")
+        w_sel = token_weight[s_idx, l_idx].contiguous()
+
     flat = src_full.reshape(-1)
     uniq, seg_off, pos_sorted, a, b = _tables(flat, max(n_images, 1) * n_img_tokens)
     return SplicePlan(S=S, L=L, n_seq=S, src=flat.to(torch.int32), labels=lab_full, sel_idx=sel, tgt=tgt,
                       seq_off=seq_off, seq_of_row=s_idx.to(torch.int32), uniq_ids=uniq, seg_off=seg_off,
                       pos_sorted=pos_sorted, feat_src_a=a, feat_src_b=b, n_sel=int(sel.numel()),
-                      n_real_tokens=int(sum(x.numel() for x in rows_src)), n_tokens=S * L)
+                      n_real_tokens=int(sum(x.numel() for x in rows_src)), n_tokens=S * L, w_sel=w_sel)
 
 
 def build_packed_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_tokens: int, n_images: int,
-                      max_len: Optional[int], pad_token_id: int = 0, splicer=None, pad_free: bool = False) -> SplicePlan:
+                      max_len: Optional[int], pad_token_id: int = 0, splicer=None, pad_free: bool = False,
+                      token_weight: Optional[torch.Tensor] = None) -> SplicePlan:
     """One row per pair: [shared prefix | chosen branch | rejected branch] (module docstring).
     input_ids / labels: [2B, T], wins then rejects.
     ``pad_free``: the B packed rows are CONCATENATED (row b starts at row_off[b], no inter-row padding) instead of being
@@ -211,10 +248,13 @@ def build_packed_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_token
     SURVEY 8a property (i) (a sequence's log-prob does not depend on its padding or its batch mates) makes dropping those rows
     exact.  Everything token-major (GEMMs, norms, SwiGLU, LM head, splice, embedding gradient) simply sees fewer rows; the
     attention kernels take (row_off, row_len) and the RoPE position table is indexed by buffer row.  Identical index tables up
-    to the row renumbering: selected rows / targets / sequence offsets keep their (sequence, position) order."""
+    to the row renumbering: selected rows / targets / sequence offsets keep their (sequence, position) order.
+    ``token_weight`` [2B, T-1]: chosen rows take token_weight[b, i], rejected rows token_weight[B+b, i] for the text position
+    i of the row (``w_sel``, same order as ``tgt``)."""
     input_ids = input_ids.cpu().long()
     labels = labels.cpu().long()
     S2 = input_ids.shape[0]
+    token_weight = _check_token_weight(token_weight, splicer, S2)
     if S2 % 2:
         raise ValueError("packed layout needs wins followed by the same number of rejects")
     B = S2 // 2
@@ -231,6 +271,7 @@ def build_packed_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_token
     packed_src, packed_pos, shs, e1s = [], [], [], []
     sel_rows: List[List[torch.Tensor]] = [[None] * B, [None] * B]          # [branch][pair] -> row offsets in the packed row
     sel_tgts: List[List[torch.Tensor]] = [[None] * B, [None] * B]
+    sel_w: List[List[torch.Tensor]] = [[None] * B, [None] * B]
     for b in range(B):
         cs, cl, rs, rl = rows_src[b], rows_lab[b], rows_src[B + b], rows_lab[B + b]
         n = min(cs.numel(), rs.numel())
@@ -248,6 +289,8 @@ def build_packed_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_token
         assert (ri >= sh).all() and (ci >= sh).all() or sh == 0
         sel_rows[0][b], sel_tgts[0][b] = ci, cl[1:][ci]
         sel_rows[1][b], sel_tgts[1][b] = Lc + (ri - sh), rl[1:][ri]
+        if token_weight is not None:
+            sel_w[0][b], sel_w[1][b] = _gather_weight(token_weight, b, ci), _gather_weight(token_weight, B + b, ri)
     L = max(int(x.numel()) for x in packed_src)
     lens = [int(x.numel()) for x in packed_src]
     if pad_free:
@@ -267,9 +310,11 @@ def build_packed_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_token
             src_full[b, :n] = packed_src[b]
             pos_full[b, :n] = packed_pos[b]
         flat, pos_flat = src_full.reshape(-1), pos_full.reshape(-1)
-    sel, tgt, seq_of, counts = [], [], [], []
+    sel, tgt, seq_of, counts, ws = [], [], [], [], []
     for br in range(2):
         for b in range(B):
+            if token_weight is not None:
+                ws.append(sel_w[br][b])
             sel.append(starts[b] + sel_rows[br][b])
             tgt.append(sel_tgts[br][b])
             seq_of.append(torch.full((sel_rows[br][b].numel(),), br * B + b, dtype=torch.int64))
@@ -286,4 +331,5 @@ def build_packed_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_token
                       seg_sh=torch.tensor(shs, dtype=torch.int32), seg_e1=torch.tensor(e1s, dtype=torch.int32),
                       shared_len=shs, n_real_tokens=int(sum(lens)), n_tokens=n_tokens,
                       row_off=torch.tensor(starts, dtype=torch.int32) if pad_free else None,
-                      row_len=torch.tensor(lens, dtype=torch.int32) if pad_free else None)
+                      row_len=torch.tensor(lens, dtype=torch.int32) if pad_free else None,
+                      w_sel=torch.cat(ws).contiguous() if token_weight is not None else None)

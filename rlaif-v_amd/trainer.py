@@ -2,7 +2,7 @@
 
 Mirrors /root/reference muffin/train/trainers.py:
   dpo_loss                  :91-126     -> rv_dpo_loss (loss, rewards and the closed-form gradient)
-  get_beta_and_logps        :161-275    -> LlavaDPOModel.forward_logps (is_llava15 branch)
+  get_beta_and_logps        :161-275    -> LlavaDPOModel.forward_logps (is_llava15 and generic / token-weighted branches)
   collect_preference_metrics:140-158    -> same metric names, computed on device, ONE fused all-reduce
                                            instead of 7 x (_nested_gather + .item()) per step (C2)
   LLaVA15DPOTrainer.compute_loss :279-311
@@ -154,15 +154,19 @@ def dpo_loss(policy_chosen_logps, policy_rejected_logps, reference_chosen_logps,
 
 def get_beta_and_logps(data_dict: Dict, model: LlavaDPOModel, args, is_minicpm: bool = False,
                        is_llava15: bool = True, save_for_backward: bool = True):
-    """trainers.py:161-275 for the LLaVA-1.5 branch.  Consumes the collator's batch dict (keys popped
-    like the reference does) and returns (policy_win_logp, policy_rej_logp, ref_win_logp, ref_rej_logp,
-    beta).  The StepOutput needed for backward is left on ``model.last_out``."""
-    if not is_llava15 or is_minicpm:
-        raise NotImplementedError("only the LLaVA-1.5 DPO branch is implemented (SURVEY.md section 8f.4)")
+    """trainers.py:161-275: the LLaVA-1.5 branch (``is_llava15``) and the generic branch (OmniLMM, ``_generic_beta_and_logps``).
+    Consumes the collator's batch dict (keys popped like the reference does) and returns (policy_win_logp, policy_rej_logp,
+    ref_win_logp, ref_rej_logp, beta).  The StepOutput needed for backward is left on ``model.last_out``."""
+    if is_minicpm:
+        raise NotImplementedError("is_minicpm: this project has no MiniCPM-V model (its pre-shifted label convention and "
+                                  "context-id keys, trainers.py:185-189, have nothing to run on)")
     if args.task != "DPO":
         raise NotImplementedError("task must be DPO (the KTO image branch is unused by the shipped scripts)")
+    if not is_llava15:
+        return _generic_beta_and_logps(data_dict, model, args, save_for_backward)
     if args.dpo_token_weighted:
-        raise NotImplementedError          # the reference raises here too for LLaVA-1.5 (trainers.py:246-248)
+        raise NotImplementedError("dpo_token_weighted with LLaVA-1.5: the token weights have the text length, the spliced "
+                                  "log-probs do not (the reference raises here too, trainers.py:246-248)")
     for k in ("win_labels", "rej_labels", "win_attention_mask", "rej_attention_mask", "ref_win_per_token_logp",
               "ref_rej_per_token_logp", "concatenated_attention_mask", "win_token_weight", "rej_token_weight",
               "concatenated_token_weight"):
@@ -189,6 +193,60 @@ def get_beta_and_logps(data_dict: Dict, model: LlavaDPOModel, args, is_minicpm: 
             ref_rej_logp.to(dev, torch.float32).contiguous(), beta)
 
 
+def _generic_beta_and_logps(data_dict: Dict, model: LlavaDPOModel, args, save_for_backward: bool):
+    """The generic branch of get_beta_and_logps (trainers.py:161-275 with is_llava15=False, is_minicpm=False): forward_DPO on
+    the concatenated batch, and with ``dpo_token_weighted`` the weighted log-probs of compute_weighted_logp (:128-137) for the
+    policy and the reference.  The policy's weighted sums come from the training step itself: the plan carries the weights
+    of the selected rows, rv_seq_sum returns the weighted sum and count, rv_row_coef scales the backward coefficients."""
+    if not getattr(model, "splice_keeps_positions", False):
+        raise ValueError("the generic get_beta_and_logps branch needs a model whose image splice keeps the text positions "
+                         "(OmniLMM); LLaVA-1.5 goes through is_llava15=True")
+    win_input_ids = data_dict.pop("win_input_ids")
+    rej_input_ids = data_dict.pop("rej_input_ids")
+    win_labels = data_dict.pop("win_labels")
+    rej_labels = data_dict.pop("rej_labels")
+    data_dict.pop("win_attention_mask", None)
+    data_dict.pop("rej_attention_mask", None)
+    ref_win_avg_logp = data_dict.pop("ref_win_avg_logp")
+    ref_rej_avg_logp = data_dict.pop("ref_rej_avg_logp")
+    ref_win_logp = data_dict.pop("ref_win_logp")
+    ref_rej_logp = data_dict.pop("ref_rej_logp")
+    ref_win_per_token_logp = data_dict.pop("ref_win_per_token_logp", None)
+    ref_rej_per_token_logp = data_dict.pop("ref_rej_per_token_logp", None)
+    if args.dpo_use_average:
+        ref_win_logp, ref_rej_logp = ref_win_avg_logp, ref_rej_avg_logp
+    beta = data_dict.pop("beta")
+    images = data_dict.pop("images")             # the B distinct images: the model encodes them once (reference: cat([images] * 2))
+    ids = data_dict.pop("concatenated_input_ids")
+    labels = data_dict.pop("concatenated_labels")
+    data_dict.pop("concatenated_attention_mask", None)           # trainers.py:198-199: replaced by None
+    win_token_weight = data_dict.pop("win_token_weight", None)
+    rej_token_weight = data_dict.pop("rej_token_weight", None)
+    concatenated_token_weight = data_dict.pop("concatenated_token_weight", None)
+    B = win_input_ids.shape[0]
+    assert B == rej_input_ids.shape[0]
+    tw = args.dpo_token_weighted
+    if tw and any(t is None for t in (ref_win_per_token_logp, ref_rej_per_token_logp, win_token_weight, rej_token_weight,
+                                      concatenated_token_weight)):
+        raise KeyError("dpo_token_weighted needs ref_*_per_token_logp and *_token_weight in the batch (DPOCollator)")
+    out = model.forward_logps(ids, labels, images, save_for_backward=save_for_backward,
+                              token_weight=concatenated_token_weight if tw else None)
+    model.last_out = out
+    logp = out.seq_logp / out.seq_cnt if args.dpo_use_average else out.seq_logp
+    dev = model.device
+    if tw:
+        # the collator's tensors are host tensors: compute_weighted_logp reduces on the device its log-probs live on
+        ref_win_logp = compute_weighted_logp(ref_win_per_token_logp.to(dev), win_labels, win_token_weight, args.dpo_use_average)
+        ref_rej_logp = compute_weighted_logp(ref_rej_per_token_logp.to(dev), rej_labels, rej_token_weight, args.dpo_use_average)
+        # trainers.py:263-271 (print + exit()): one host sync, before anything reaches backward / flat_g / AdamW
+        bad = torch.stack([torch.isnan(ref_win_logp).any(), torch.isnan(ref_rej_logp).any(), torch.isnan(logp).any()]).tolist()
+        for name, b in zip(("ref_win_logp", "ref_rej_logp", "concatenated_logp"), bad):
+            if b:
+                raise FloatingPointError(f"{name} is NaN (token-weighted DPO)")
+    return (logp[:B], logp[B:], ref_win_logp.to(dev, torch.float32).contiguous(),
+            ref_rej_logp.to(dev, torch.float32).contiguous(), beta)
+
+
 class GradReducer:
     """Interface of the data-parallel gradient exchange (see rlaif_v_amd.dist.BucketedAllReduce)."""
     world_size = 1
@@ -206,6 +264,7 @@ class GradReducer:
 class LLaVA15DPOTrainer:
     """``LLaVA15DPOTrainer(model=, tokenizer=, args=, train_dataset=, eval_dataset=, data_collator=)``
     then ``.train()`` - the call surface of muffin/train/train_llava15.py:320-334."""
+    is_llava15 = True                   # which get_beta_and_logps branch compute_loss takes (OmniLMMDPOTrainer: the generic one)
 
     def __init__(self, model: LlavaDPOModel, tokenizer=None, args: Optional[TrainingArguments] = None,
                  train_dataset=None, eval_dataset=None, data_collator: Optional[Callable] = None,
@@ -251,10 +310,10 @@ class LLaVA15DPOTrainer:
         """trainers.py:281-311.  Returns the 0-d loss tensor (device).  Metrics are left on the device
         (``self._pending_metrics``) and reduced/logged without a per-metric host sync."""
         if self.args.past_index >= 0:
-            raise NotImplementedError
+            raise NotImplementedError("past_index >= 0: the reference raises here too (trainers.py:282-283)")
         data_dict = inputs
         policy_win, policy_rej, ref_win, ref_rej, beta = get_beta_and_logps(
-            data_dict, model, self.args, is_llava15=True, save_for_backward=model.training)
+            data_dict, model, self.args, is_llava15=self.is_llava15, save_for_backward=model.training)
         out: StepOutput = model.last_out
         sft_w = float(os.environ.get("SFT_weight", 0.0))      # trainers.py:299-300 (read on every call)
         dpo_w = float(os.environ.get("DPO_weight", 1.0))
@@ -548,3 +607,16 @@ class LLaVA15DPOTrainer:
         self.state = dict(dict(epoch=0, batches_in_epoch=0), **blob["state"])
         self.model._dropout_step = int(blob.get("dropout_step", 0))
         self._micro = 0
+
+
+class OmniLMMDPOTrainer(LLaVA15DPOTrainer):
+    """The DPO trainer of an OmniLMM model (``OmniLMMDPOModel``): ``compute_loss`` runs the generic branch of
+    get_beta_and_logps (trainers.py:161-275 with is_llava15=False), the only branch where ``--dpo_token_weighted`` works.
+    Accumulation, the data-parallel reducer, LoRA, checkpointing and the metrics (the weighted log-probs when token
+    weighted, as collect_preference_metrics reports them) are LLaVA15DPOTrainer's."""
+    is_llava15 = False
+
+    def __init__(self, model: LlavaDPOModel, *args, **kwargs):
+        if not getattr(model, "splice_keeps_positions", False):
+            raise ValueError("OmniLMMDPOTrainer needs a model whose image splice keeps the text positions (OmniLMMDPOModel)")
+        super().__init__(model, *args, **kwargs)
