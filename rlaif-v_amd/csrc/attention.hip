@@ -49,15 +49,6 @@ __device__ __forceinline__ void mfma_agpr_zero(f32x16_t& acc) {
 // v_permlane32_swap instead of __shfl_xor: hipcc lowers the shuffle to ds_bpermute_b32 + s_waitcnt lgkmcnt(0), and that wait
 // also drains every fragment read issued ahead of it (the V^T prefetch of the forward's softmax section).  With both operands
 // = x the swap leaves {own, partner} in lanes < 32 and {partner, own} in lanes >= 32: the combination is symmetric.
-#ifndef RV_ATTN_PERMLANE
-#define RV_ATTN_PERMLANE 1
-#endif
-#ifndef RV_ATTN_FWD_NW_DEFAULT
-#define RV_ATTN_FWD_NW_DEFAULT 4
-#endif
-#ifndef RV_ATTN_FWD_DEFAULT
-#define RV_ATTN_FWD_DEFAULT 2      // forward kernel at head dim 128: 2 = attn_fwd2_kernel, 3 = attn_fwd3_kernel (attn_fwd3.inc)
-#endif
 __device__ __forceinline__ void xhalf_pair(float x, float& a, float& b) {
   typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
   const unsigned u = __builtin_bit_cast(unsigned, x);
@@ -66,39 +57,16 @@ __device__ __forceinline__ void xhalf_pair(float x, float& a, float& b) {
   b = __builtin_bit_cast(float, (unsigned)r[1]);
 }
 __device__ __forceinline__ float xhalf_max(float x) {
-#if RV_ATTN_PERMLANE
   float a, b;
   xhalf_pair(x, a, b);
   return fmaxf(a, b);
-#else
-  return fmaxf(x, __shfl_xor(x, 32, 64));
-#endif
 }
 __device__ __forceinline__ float xhalf_sum(float x) {
-#if RV_ATTN_PERMLANE
   float a, b;
   xhalf_pair(x, a, b);
   return a + b;
-#else
-  return x + __shfl_xor(x, 32, 64);
-#endif
 }
 
-// RV_ATTN_PROF (experiment builds): s_memtime stamps in the tile loops of the forward (slots 0..7) and dQ (slots 8..15) kernels,
-// accumulated per wave 0 of every workgroup into rv_attn_prof[]: +0 DMA issue, +1 first MFMA phase (S^T [and dP^T]),
-// +2 softmax / dS + second MFMA phase, +3 wait for the next tile's DMA, +4 barrier, +5 per-pass prologue / epilogue, +6 whole
-// kernel, +7 workgroups.  tools/exp_attn_prof.py reads them.  Each stamp drains lgkmcnt (s_memtime is an SMEM read).
-#ifdef RV_ATTN_PROF
-__device__ unsigned long long rv_attn_prof[16];
-#define APROF_DECL unsigned apr[6] = {0, 0, 0, 0, 0, 0}; const unsigned long long apr_t0 = __builtin_amdgcn_s_memtime(); unsigned long long apr_last = apr_t0;
-#define APROF(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); apr[i] += (unsigned)(t_ - apr_last); apr_last = t_; }
-#define APROF_END(base) if (threadIdx.x == 0) { for (int i_ = 0; i_ < 6; ++i_) atomicAdd(&rv_attn_prof[(base) + i_], (unsigned long long)apr[i_]); \
-    atomicAdd(&rv_attn_prof[(base) + 6], __builtin_amdgcn_s_memtime() - apr_t0); atomicAdd(&rv_attn_prof[(base) + 7], 1ull); }
-#else
-#define APROF_DECL
-#define APROF(i)
-#define APROF_END(base)
-#endif
 #define LOG2E 1.4426950408889634f
 #define LN2 0.6931471805599453f
 
@@ -316,25 +284,13 @@ struct TileDma {
   }
 };
 
-// ABL (experiment builds, -DRV_ATTN_EXPERIMENTS; results WRONG by construction): 1 = no softmax arithmetic, 2 = no PV MFMAs,
-// 3 = no QK^T MFMAs, 6 = no LDS-DMA of the following tiles.
-#ifndef RV_DKV_S2
-#define RV_DKV_S2 1            // dK/dV kernel: S^T accumulated as two independent partial sums (0: one 8-deep dependent chain)
-#endif
-#ifndef RV_ATTN_SMSPLIT
-#define RV_ATTN_SMSPLIT 1      // softmax / dS slices computed under the MFMAs of the previous slice (round 3: forward -2.7 %)
-#endif
-#ifndef RV_ATTN_FWD_PRIO
-#ifndef RV_ATTN_DQ_PRIO
-#define RV_ATTN_DQ_PRIO 0      // 1 = s_setprio 1 in the dQ kernel's MFMA phases (experiment, round 4)
-#endif
-#define RV_ATTN_FWD_PRIO 1     // 1 = s_setprio 1 in the QK^T / PV MFMA phases (measured -0.5..-3 % vs 0, profiles/r02_attn_fwd_prio.log); 2 = in the softmax section (+1..2 %)
-#endif
+// The MFMA phases (QK^T, PV) run at s_setprio 1: -0.5..-3 % time against no priority changes; priority 1 in the softmax section
+// instead cost +1..2 % (profiles/r02_attn_fwd_prio.log).
 // NW = waves per workgroup = 32-query slices that share one K / V ring (round 5).  NW = 4: 128 queries, two workgroups per CU
 // (rounds 1-4).  NW = 8: 256 queries, ONE workgroup per CU - every K / V tile is staged once per 256 queries, i.e. HALF the LDS-DMA
 // instructions per CU and key tile (each wave issues 4 instead of 8): the phase stamps of round 4 put 18 % of a tile in those issues,
 // which the CU's address path serves one wave-instruction at a time (profiles/r04_attn_fwd_dq_phase_profile.log).
-template <int HD, bool CAUSAL, int ABL = 0, int NW = 4>
+template <int HD, bool CAUSAL, int NW = 4>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(const bf16_t* __restrict__ qkv, long ld, int q_col0,
                                                            int k_col0, int v_col0, bf16_t* __restrict__ out, long ldo,
                                                            float* __restrict__ lse, int Lmax, int H, int nx, float scale,
@@ -373,7 +329,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
 
   int blk_first, blk_second;
   pair_blocks<false, BQ>(bx, nqb, L, sh, e1, lane, CAUSAL && ((nx >> 20) & 1), CAUSAL && ((nx >> 21) & 1), blk_first, blk_second);
-  APROF_DECL
   const int npass = CAUSAL ? 2 : 1;
   for (int pass = 0; pass < npass; ++pass) {
     const int qb = (pass == 0) ? blk_first : blk_second;
@@ -410,18 +365,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    APROF(5);
     for (int i = 0; i < nte; ++i) {
       const int t = i < skip_lo ? i : i + skip_n;
       const int k0 = t * 64;
       const uint8_t* Ks = smem + (i & 1) * STAGE;
       const uint8_t* Vs = Ks + TILE;
-      if (i + 1 < nte && ABL != 6) {
+      if (i + 1 < nte) {
         const int kn = ((i + 1 < skip_lo) ? i + 1 : i + 1 + skip_n) * 64;
         dma.issue(kbase, ld, tok0, kn, L, smem + ((i + 1) & 1) * STAGE, wave);
         dma.issue(vbase, ld, tok0, kn, L, smem + ((i + 1) & 1) * STAGE + TILE, wave);
       }
-      APROF(0);
       if (!(CAUSAL && k0 > q0w + 31) && !(q0w >= e1 && k0 >= sh && k0 + 63 < e1)) {
         // S^T = K Q^T.  The K fragments are fetched in groups of four explicit ds_read_b128, group g+1 in flight while
         // group g multiplies (the compiler's own schedule was read / wait / MFMA sixteen times per tile).  Fragment ks of
@@ -432,7 +385,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
         zero16(sacc[0]);
         zero16(sacc[1]);
         bf16x8_t kA[4], kB[4];                       // element j of a group: half kt = j & 1, k step 2 g + (j >> 1)
-        if (RV_ATTN_FWD_PRIO == 1) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int j = 0; j < 4; ++j) kA[j] = ds_read_b128_asm(ka0 ^ (uint32_t)((j >> 1) << 5), (j & 1) * 32 * HD * 2);
 #pragma unroll
@@ -450,13 +403,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int j = 0; j < 4; ++j) {   // the two halves alternate: consecutive MFMAs never share an accumulator
-            if (ABL == 3) { asm volatile("" ::"v"(kcur[j])); continue; }
             sacc[j & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kcur[j], qf[2 * g + (j >> 1)], sacc[j & 1], 0, 0, 0);
           }
         }
         // The tile needs element masks only when it touches the sequence end, the causal diagonal of this wave
         // or the chosen-branch window of a packed pair; interior tiles (the vast majority) skip ~200 VALU ops.
-        APROF(1);
         const bool need_mask = (k0 + 63 >= L) || (CAUSAL && k0 + 63 > q0w) ||
                                (q0w + 31 >= e1 && k0 + 63 >= sh && k0 < e1);
         if (need_mask) {
@@ -467,8 +418,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
         // the softmax VALU work; afterwards the fragments of 16-key group kk+1 are in flight while group kk multiplies.
         const uint32_t vs_addr = lds_addr_of(Vs);
         bf16x8_t vA[ET], vB[ET];
-        if (RV_ATTN_FWD_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-        if (RV_ATTN_FWD_PRIO == 2) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(0);
 #pragma unroll
         for (int e = 0; e < ET; ++e) vA[e] = tro.read(vs_addr, 0, e);
         // (Round 3 tried the same arithmetic with the instruction-level parallelism spelled out - four independent maxima, all 32
@@ -476,7 +426,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
         // v_fma -> v_exp pairs and one 32-deep v_add chain: no measurable change, profiles/r03_attn_rounds_softmax_ilp.log - the
         // second wave of the SIMD already fills those bubbles; removed.)
         float tmax = -INFINITY;                      // raw-score maximum (c > 0 keeps the order)
-        if (ABL != 1)
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -485,7 +434,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
         const float m_new = fmaxf(m_run, tmax * c);
         const float alpha = (m_new == -INFINITY) ? 1.f : __builtin_amdgcn_exp2f(m_run - m_new);   // row still empty
         const float neg_m = (m_new == -INFINITY) ? 0.f : -m_new;     // a fully masked row keeps p = exp2(-inf) = 0
-#if RV_ATTN_SMSPLIT
         // Exponentials in four slices of 16 keys, each computed UNDER the PV MFMAs of the previous slice (the matrix pipe runs
         // asynchronously: between two MFMA issues of a wave ~5 VALU slots are free): slice kk+1's 8 v_fma / v_exp / v_add go two
         // per MFMA of slice kk.  Only the maximum has to be complete before the first exponential.
@@ -500,7 +448,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
         auto exp_slice = [&](int kk, int j0, int j1) {      // elements j0..j1-1 (of 8) of slice kk
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
-            if (j < j0 || j >= j1 || ABL == 1) continue;
+            if (j < j0 || j >= j1) continue;
             const int r = (kk & 1) * 8 + j;
             const float p = __builtin_amdgcn_exp2f(fmaf(sacc[kk >> 1][r], c, neg_m));
             sacc[kk >> 1][r] = p;
@@ -508,8 +456,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
           }
         };
         exp_slice(0, 0, 8);
-        if (RV_ATTN_FWD_PRIO == 1) __builtin_amdgcn_s_setprio(1);
-        if (RV_ATTN_FWD_PRIO == 2) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
           const bf16x8_t pf = pack_frag(sacc[kk >> 1], (kk & 1) * 8);
@@ -525,7 +472,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int e = 0; e < ET; ++e) {
-            if (ABL != 2) o[e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vcur[e], pf, o[e], 0, 0, 0);
+            o[e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vcur[e], pf, o[e], 0, 0, 0);
             if (kk < 3) {
               exp_slice(kk + 1, (8 / ET) * e, (8 / ET) * (e + 1));
               __builtin_amdgcn_sched_barrier(0);              // keep the slice pieces between the MFMAs
@@ -535,55 +482,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
         psum = xhalf_sum(psum);
         l_run = l_run * alpha + psum;
       }
-#else
-        float psum = 0.f;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            if (ABL == 1) continue;
-            const float p = __builtin_amdgcn_exp2f(fmaf(sacc[kt][r], c, neg_m));   // one v_fma + one v_exp
-            sacc[kt][r] = p;
-            psum += p;
-          }
-        psum = xhalf_sum(psum);
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-        if (!__all(alpha == 1.0f)) {                // the running maximum rarely moves after the first tiles
-#pragma unroll
-          for (int e = 0; e < ET; ++e)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[e][r] *= alpha;
-        }
-        if (RV_ATTN_FWD_PRIO == 1) __builtin_amdgcn_s_setprio(1);
-        if (RV_ATTN_FWD_PRIO == 2) __builtin_amdgcn_s_setprio(0);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-          const bf16x8_t pf = pack_frag(sacc[kk >> 1], (kk & 1) * 8);
-          bf16x8_t (&vcur)[ET] = (kk & 1) ? vB : vA;
-          bf16x8_t (&vnxt)[ET] = (kk & 1) ? vA : vB;
-          if (kk < 3) {
-#pragma unroll
-            for (int e = 0; e < ET; ++e) vnxt[e] = tro.read(vs_addr, (kk + 1) * 16, e);
-            asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * ET) : "memory");   // everything older than the 2*ET reads just issued
-          } else {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int e = 0; e < ET; ++e) {
-            if (ABL == 2) { asm volatile("" ::"v"(vcur[e]), "v"(pf)); continue; }
-            o[e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vcur[e], pf, o[e], 0, 0, 0);
-          }
-        }
-      }
-#endif
-      if (RV_ATTN_FWD_PRIO == 1) __builtin_amdgcn_s_setprio(0);
-      APROF(2);
+      __builtin_amdgcn_s_setprio(0);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      APROF(3);
       __syncthreads();
-      APROF(4);
     }
 
     if (q < L) {
@@ -601,8 +502,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
       if (half == 0) lse[((long)s * H + h) * Lmax + q] = (m_run + log2f(l_run)) * LN2;
     }
   }  // pass
-  APROF(5);
-  APROF_END(0)
 }
 
 // Inverse RoPE fused into the stores of dQ / dK (apply_rotary_pos_emb's autograd, HF modeling_llama: the half-split pairs
@@ -673,7 +572,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(const bf16_t* __re
 
   int blk_first, blk_second;
   pair_blocks<false>(bx, nqb, L, sh, e1, lane, CAUSAL && ((nx >> 20) & 1), CAUSAL && ((nx >> 21) & 1), blk_first, blk_second);
-  APROF_DECL
   const int npass = CAUSAL ? 2 : 1;
   for (int pass = 0; pass < npass; ++pass) {
     const int qb = (pass == 0) ? blk_first : blk_second;
@@ -736,7 +634,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(const bf16_t* __re
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    APROF(5);
     for (int i = 0; i < nte; ++i) {
       const int t = i < skip_lo ? i : i + skip_n;
       const int k0 = t * 64;
@@ -747,7 +644,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(const bf16_t* __re
         dma.issue(kbase, ld, tok0, kn, L, smem + ((i + 1) & 1) * STAGE, wave);
         dma.issue(vbase, ld, tok0, kn, L, smem + ((i + 1) & 1) * STAGE + TILE, wave);
       }
-      APROF(0);
       if (!(CAUSAL && k0 > q0w + 31) && !(q0w >= e1 && k0 >= sh && k0 + 63 < e1)) {
         const uint32_t ka0 = lds_addr_of(Ks) + boff[0];       // fragment ks: ka0 ^ (ks << 5); V tile = K tile + TILE
 #pragma unroll
@@ -763,7 +659,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(const bf16_t* __re
 #pragma unroll
             for (int j = 0; j < 2; ++j)
               fr3[p][j] = ds_read_b128_asm(ka0 ^ (uint32_t)(p << 5), j * TILE + kt * 32 * HD * 2);
-          if (RV_ATTN_DQ_PRIO == 1) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) {
             if (ks + 2 < KS) {
@@ -780,7 +675,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(const bf16_t* __re
             sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr3[ks % 3][0], qf[ks], sacc, 0, 0, 0);
             pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fr3[ks % 3][1], dof[ks], pacc, 0, 0, 0);
           }
-          if (RV_ATTN_DQ_PRIO == 1) __builtin_amdgcn_s_setprio(0);
           // K^T fragments of the first 16 keys: independent of dS, requested before the exp section (latency hidden)
           const uint32_t ks_addr = lds_addr_of(Ks);
           bf16x8_t kfr0[ET], kfr1[ET];
@@ -802,7 +696,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(const bf16_t* __re
 #pragma unroll
             for (int e = 0; e < ET; ++e) kfr1[e] = tro.read(ks_addr, kt * 32 + 16, e);
             asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * ET) : "memory");     // kfr0 landed; kfr1 may still be in flight
-            if (RV_ATTN_DQ_PRIO == 1) __builtin_amdgcn_s_setprio(1);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int e = 0; e < ET; ++e) dq[e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr0[e], df, dq[e], 0, 0, 0);
@@ -813,15 +706,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(const bf16_t* __re
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int e = 0; e < ET; ++e) dq[e] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr1[e], df, dq[e], 0, 0, 0);
-            if (RV_ATTN_DQ_PRIO == 1) __builtin_amdgcn_s_setprio(0);
           }
         }
       }
-      APROF(2);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      APROF(3);
       __syncthreads();
-      APROF(4);
     }
 
     if (q < L) {
@@ -843,8 +732,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(const bf16_t* __re
       }
     }
   }  // pass
-  APROF(5);
-  APROF_END(8)
 }
 
 // =============================================================================================
@@ -877,10 +764,7 @@ __device__ __forceinline__ uint32_t qtile_off(int row, int c) {
 // =============================================================================================
 #include "attn_agpr.inc"
 
-// ABL (experiment builds only, -DRV_ATTN_EXPERIMENTS; results are WRONG by construction): 1 = no exp / dS arithmetic,
-// 2 = no dV / dK MFMAs, 3 = no S / dP MFMAs, 4 = no transposing LDS reads, 5 = no row-fragment LDS reads, 6 = no DMA of the
-// next tile.  Timing deltas against ABL 0 price the stages (cdna_hip_programming.md 5.4 rule 17: values stay live).
-template <bool CAUSAL, int ABL = 0>
+template <bool CAUSAL>
 __global__ __launch_bounds__(256, 1) void attn_bwd_dkv3_kernel(const bf16_t* __restrict__ qkv, long ld, int q_col0,
                                                                int k_col0, int v_col0,
                                                                const bf16_t* __restrict__ dO, long lddo,
@@ -920,7 +804,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv3_kernel(const bf16_t* __r
   // SIMD nothing else would run meanwhile, so the pieces are issued one by one BETWEEN the MFMAs of the dV / dK segment,
   // whose matrix work keeps executing underneath.
   auto issue_piece = [&](int hq, int t, int buf, int j) {
-    if (ABL == 6 && t > 0) return;
     uint8_t* st = smem + buf * STAGE;
     // the tile index goes through an opaque scalar: the address arithmetic below is then computed HERE (a handful of
     // 32-bit VALU in the shadow of the surrounding MFMAs) instead of being hoisted to the top of the tile, where nine
@@ -1031,7 +914,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv3_kernel(const bf16_t* __r
           // cannot issue before that result exists (16 passes) while independent ones issue every 8 - a single 8-deep chain
           // runs at half rate.  The halves are added inside the exponent's argument.
           f32x16_t sacc2;
-#if RV_DKV_S2
           smfma_first<0>(sacc, fq[0]);
           smfma_first<1>(sacc2, fq[1]);
           static_for<3>([&](auto ic) {
@@ -1039,11 +921,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv3_kernel(const bf16_t* __r
             smfma<ks>(sacc, fq[ks]);
             smfma<ks + 1>(sacc2, fq[ks + 1]);
           });
-#else
-          smfma_first<0>(sacc, fq[0]);
-          static_for<KS - 1>([&](auto ic) { smfma<decltype(ic)::value + 1>(sacc, fq[decltype(ic)::value + 1]); });
-          zero16(sacc2);
-#endif
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the dO fragments landed under the chain above
           __builtin_amdgcn_sched_barrier(0);
           // lse and delta of this lane's 16 queries (4 consecutive floats per accumulator row group), then the transposed
@@ -1115,10 +992,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv3_kernel(const bf16_t* __r
           __builtin_amdgcn_sched_barrier(0);
           static_for<ET>([&](auto ic) {
             constexpr int e = decltype(ic)::value;
-            if (ABL == 2) asm volatile("" ::"v"(dotf0[e]), "v"(pf0), "v"(qtf0[e]), "v"(dsf0));
-            if (ABL != 2) acc_mfma<4 + e>(dotf0[e], pf0);
+            acc_mfma<4 + e>(dotf0[e], pf0);
             if (qt == 0) { __builtin_amdgcn_sched_barrier(0); issue_piece(hq, tn, BUF ^ 1, 2 * e); __builtin_amdgcn_sched_barrier(0); }
-            if (ABL != 2) acc_mfma<e>(qtf0[e], dsf0);
+            acc_mfma<e>(qtf0[e], dsf0);
             if (qt == 0) { __builtin_amdgcn_sched_barrier(0); issue_piece(hq, tn, BUF ^ 1, 2 * e + 1); __builtin_amdgcn_sched_barrier(0); }
           });
 #pragma unroll
@@ -1135,18 +1011,12 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv3_kernel(const bf16_t* __r
             asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");   // dotf1 landed
           }
           __builtin_amdgcn_sched_barrier(0);
-          static_for<ET>([&](auto ic) {
-            if (ABL == 2) { asm volatile("" ::"v"(dotf1[decltype(ic)::value]), "v"(pf1)); return; }
-            acc_mfma<4 + decltype(ic)::value>(dotf1[decltype(ic)::value], pf1);
-          });
+          static_for<ET>([&](auto ic) { acc_mfma<4 + decltype(ic)::value>(dotf1[decltype(ic)::value], pf1); });
           if (qt == 0) { __builtin_amdgcn_sched_barrier(0); issue_piece(hq, tn, BUF ^ 1, 8); __builtin_amdgcn_sched_barrier(0); }
           if (qt == 0) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");   // qtf1 landed (batch 0 of sub-tile 1 may be in flight)
           else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           __builtin_amdgcn_sched_barrier(0);
-          static_for<ET>([&](auto ic) {
-            if (ABL == 2) { asm volatile("" ::"v"(qtf1[decltype(ic)::value]), "v"(dsf1)); return; }
-            acc_mfma<decltype(ic)::value>(qtf1[decltype(ic)::value], dsf1);
-          });
+          static_for<ET>([&](auto ic) { acc_mfma<decltype(ic)::value>(qtf1[decltype(ic)::value], dsf1); });
         }
       }
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -1222,15 +1092,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv3_kernel(const bf16_t* __r
 // operands read behind it, a FOUR-stage LDS ring (133 KB) fetched two tiles ahead, transposed fragments two groups ahead.
 // =============================================================================================
 #define BF(x) __builtin_bit_cast(bf16x8_t, x)
-// RV_DKV5_PROF (experiment builds): s_memtime stamps at the phase boundaries of a tile, accumulated per wave 0 of every workgroup
-// into rv_dkv5_prof[] (ticks): 0 skipped-tile / loop glue, 1 P1, 2 P2, 3 P3, 4 P4, 5 end-of-tile waits, 6 barrier, 7 prologue +
-// epilogue of a pass, 14 whole kernel per workgroup, 15 workgroups.  Each stamp drains lgkmcnt (s_memtime is an SMEM read).
-#ifdef RV_DKV5_PROF
-__device__ unsigned long long rv_dkv5_prof[16];
-#define PROF(i) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); pr[i] += (unsigned)(t_ - pr_last); pr_last = t_; }
-#else
-#define PROF(i)
-#endif
 template <bool CAUSAL>
 __global__ __launch_bounds__(256, 1) void attn_bwd_dkv5_kernel(const bf16_t* __restrict__ qkv, long ld, int q_col0,
                                                                int k_col0, int v_col0,
@@ -1319,11 +1180,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv5_kernel(const bf16_t* __r
 
   int blk_first, blk_second;
   pair_blocks<true>(bx, nkb, L, sh, e1, lane, CAUSAL && ((nx >> 20) & 1), CAUSAL && ((nx >> 21) & 1), blk_first, blk_second);
-#ifdef RV_DKV5_PROF
-  unsigned pr[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const unsigned long long pr_t0 = __builtin_amdgcn_s_memtime();
-  unsigned long long pr_last = pr_t0;
-#endif
   // Per-pass state (a causal workgroup owns TWO key blocks: blk_first, then blk_second).  The set-up of a pass - first two tiles
   // of its LDS ring, K / V fragments of its 32 keys per wave - is issued BEFORE the epilogue of the previous pass (accumulator
   // read-out, inverse rotation, stores), so the two memory latencies and the ~600 epilogue instructions overlap; version 3 / 4
@@ -1348,7 +1204,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv5_kernel(const bf16_t* __r
       frag_load<8 + ks>(kp + v_col0 + 16 * ks);
     });
   };
-  PROF(11);
   pass_begin(blk_first);
   static_for<8>([&](auto ic) { acc_zero<decltype(ic)::value>(); });
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1363,7 +1218,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv5_kernel(const bf16_t* __r
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
       }
-      PROF(7);
       // carried from tile to tile: sub-tile A's accumulators (pre-loaded with -lse / scale and -delta), its first dO row
       // fragments (the matching Q fragments sit in AGPRs a[192:207])
       f32x16_t sA, pA;
@@ -1442,7 +1296,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv5_kernel(const bf16_t* __r
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the clamped re-fetches of the last tiles: nothing may land later
       __syncthreads();
-      PROF(8);
       const uint32_t back = (uint32_t)(buf * STAGE);       // the bases point into ring buffer `buf`: back to buffer 0
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) rb[ks] -= back;
@@ -1458,7 +1311,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv5_kernel(const bf16_t* __r
     const int out_row0 = kv0w;                  // first key row of this wave's finished tile
     const int next_blk = (pass + 1 < npass) ? blk_second : -1;
     if (next_blk >= 0) pass_begin(next_blk);
-    PROF(9);
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // last asm MFMA -> v_accvgpr_read (hipcc pads nothing for asm)
     // Read-out through LDS.  A lane owns ONE key row and 4 consecutive columns per accumulator row group: storing from registers
     // is 32 eight-byte stores per wave instruction into 32 different 24 KB-strided rows (phase stamps: 10 % of the kernel).  Each
@@ -1539,7 +1391,6 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv5_kernel(const bf16_t* __r
       if (all_rows) write_rows(std::false_type{});
       else write_rows(std::true_type{});
     }
-    PROF(10);
     if (next_blk < 0) break;
     static_for<8>([&](auto ic) { acc_zero<decltype(ic)::value>(); });
     // the next pass's K / V fragments and first tiles have landed; this pass's 16 row stores - the NEWEST vector-memory operations -
@@ -1547,19 +1398,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv5_kernel(const bf16_t* __r
     if (all_rows) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    PROF(7);
   }  // pass
-#ifdef RV_DKV5_PROF
-  if (tid == 0) {
-#pragma unroll
-    for (int i = 0; i < 12; ++i) atomicAdd(&rv_dkv5_prof[i], (unsigned long long)pr[i]);
-    atomicAdd(&rv_dkv5_prof[14], __builtin_amdgcn_s_memtime() - pr_t0);
-    atomicAdd(&rv_dkv5_prof[15], 1ull);
-  }
-#endif
 }
 #undef BF
-#undef PROF
 
 #include "attn_fwd3.inc"
 
@@ -1584,23 +1425,6 @@ int rv_set_attn_fwd_version(int version) {
 
 long rv_attn_bwd_workspace_floats(int S, int H, int L) { return 3L * S * H * L; }
 
-#ifdef RV_ATTN_PROF
-// experiment builds only: read and clear the phase counters of the forward / dQ kernels (16 x u64)
-int rv_debug_attn_prof(unsigned long long* out16) {
-  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(rv_attn_prof), 16 * sizeof(unsigned long long)) != hipSuccess) return 1;
-  unsigned long long z[16] = {0};
-  return hipMemcpyToSymbol(HIP_SYMBOL(rv_attn_prof), z, sizeof(z)) != hipSuccess;
-}
-#endif
-#ifdef RV_DKV5_PROF
-// experiment builds only: read and clear the phase counters of attn_bwd_dkv5_kernel (16 x u64)
-int rv_debug_dkv5_prof(unsigned long long* out16) {
-  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(rv_dkv5_prof), 16 * sizeof(unsigned long long)) != hipSuccess) return 1;
-  unsigned long long z[16] = {0};
-  return hipMemcpyToSymbol(HIP_SYMBOL(rv_dkv5_prof), z, sizeof(z)) != hipSuccess;
-}
-#endif
-
 int rv_attn_fwd(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, void* out, long ldo, float* lse, int S,
                 int L, int H, int hd, int causal, float scale, const int* seg_sh, const int* seg_e1, int kv_group,
                 const int* row_off, const int* row_len, void* stream) {
@@ -1615,9 +1439,9 @@ int rv_attn_fwd(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, vo
   if (map_mode < 0) { const char* e = getenv("RV_ATTN_MAP"); map_mode = e ? atoi(e) : 1; }
   hipStream_t st = (hipStream_t)stream;
   static int fwd_nw = -1;         // RV_ATTN_FWD_NW: 4 = 128-query workgroups (two per CU), 8 = 256-query workgroups on one K / V ring (hd 128)
-  if (fwd_nw < 0) { const char* e = getenv("RV_ATTN_FWD_NW"); fwd_nw = (e && atoi(e) == 8) ? 8 : RV_ATTN_FWD_NW_DEFAULT; }
-  static int fwd_env = -1;        // RV_ATTN_FWD: 3 = attn_fwd3_kernel (hd 128; csrc/attn_fwd3.inc), 2 = attn_fwd2_kernel
-  if (fwd_env < 0) { const char* e = getenv("RV_ATTN_FWD"); fwd_env = (e && (atoi(e) == 2 || atoi(e) == 3)) ? atoi(e) : RV_ATTN_FWD_DEFAULT; }
+  if (fwd_nw < 0) { const char* e = getenv("RV_ATTN_FWD_NW"); fwd_nw = (e && atoi(e) == 8) ? 8 : 4; }
+  static int fwd_env = -1;        // RV_ATTN_FWD: 3 = attn_fwd3_kernel (hd 128; csrc/attn_fwd3.inc), 2 = attn_fwd2_kernel (default)
+  if (fwd_env < 0) { const char* e = getenv("RV_ATTN_FWD"); fwd_env = (e && (atoi(e) == 2 || atoi(e) == 3)) ? atoi(e) : 2; }
   const int fwd_ver = g_fwd_override ? g_fwd_override : fwd_env;
   const bool v3 = hd == 128 && fwd_ver == 3;
   const int nw = v3 ? 8 : (hd == 128) ? fwd_nw : 4;             // version 3: 256-query blocks (4 waves x 64 rows)
@@ -1647,33 +1471,19 @@ int rv_attn_fwd(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, vo
   if (!attr_done) {
     hipFuncSetAttribute((const void*)attn_fwd2_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     hipFuncSetAttribute((const void*)attn_fwd2_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    hipFuncSetAttribute((const void*)attn_fwd2_kernel<128, true, 0, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    hipFuncSetAttribute((const void*)attn_fwd2_kernel<128, false, 0, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    hipFuncSetAttribute((const void*)attn_fwd2_kernel<128, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    hipFuncSetAttribute((const void*)attn_fwd2_kernel<128, false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
     attr_done = true;
   }
 #define LAUNCH_FWD(HD_, C_)                                                                                      \
   hipLaunchKernelGGL((attn_fwd2_kernel<HD_, C_>), grid, block, 4 * 64 * HD_ * 2, st, (const bf16_t*)qkv, ld, q_col0, \
                      k_col0, v_col0, (bf16_t*)out, ldo, lse, L, H, nx, scale, seg_sh, seg_e1, kv_group, row_off, row_len)
-#ifdef RV_ATTN_EXPERIMENTS
-  static int fwd_ablate = -1;
-  if (fwd_ablate < 0) { const char* a = getenv("RV_FWD_ABLATE"); fwd_ablate = a ? atoi(a) : 0; }
-#define LAUNCH_FWD_ABL(N)                                                                                                  \
-  if (fwd_ablate == N && hd == 128 && causal) {                                                                            \
-    hipFuncSetAttribute((const void*)attn_fwd2_kernel<128, true, N>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);     \
-    hipLaunchKernelGGL((attn_fwd2_kernel<128, true, N>), grid, block, 4 * 64 * 128 * 2, st, (const bf16_t*)qkv, ld, q_col0, \
-                       k_col0, v_col0, (bf16_t*)out, ldo, lse, L, H, nx, scale, seg_sh, seg_e1, kv_group, row_off, row_len);                   \
-    RV_CHECK_LAUNCH();                                                                                                     \
-    return 0;                                                                                                              \
-  }
-  LAUNCH_FWD_ABL(1) LAUNCH_FWD_ABL(2) LAUNCH_FWD_ABL(3) LAUNCH_FWD_ABL(6)
-#undef LAUNCH_FWD_ABL
-#endif
   if (hd == 128 && nw == 8) {
     if (causal)
-      hipLaunchKernelGGL((attn_fwd2_kernel<128, true, 0, 8>), grid, block, 4 * 64 * 128 * 2, st, (const bf16_t*)qkv, ld, q_col0, k_col0,
+      hipLaunchKernelGGL((attn_fwd2_kernel<128, true, 8>), grid, block, 4 * 64 * 128 * 2, st, (const bf16_t*)qkv, ld, q_col0, k_col0,
                          v_col0, (bf16_t*)out, ldo, lse, L, H, nx, scale, seg_sh, seg_e1, kv_group, row_off, row_len);
     else
-      hipLaunchKernelGGL((attn_fwd2_kernel<128, false, 0, 8>), grid, block, 4 * 64 * 128 * 2, st, (const bf16_t*)qkv, ld, q_col0, k_col0,
+      hipLaunchKernelGGL((attn_fwd2_kernel<128, false, 8>), grid, block, 4 * 64 * 128 * 2, st, (const bf16_t*)qkv, ld, q_col0, k_col0,
                          v_col0, (bf16_t*)out, ldo, lse, L, H, nx, scale, seg_sh, seg_e1, kv_group, row_off, row_len);
   } else if (hd == 128) { if (causal) LAUNCH_FWD(128, true); else LAUNCH_FWD(128, false); }
   else { if (causal) LAUNCH_FWD(64, true); else LAUNCH_FWD(64, false); }
@@ -1712,21 +1522,11 @@ int rv_attn_bwd(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, co
   constexpr int DKV5_LDS = 4 * (2 * 64 * 256 + 512);     // version 5: four-stage ring
   static bool attr_done = false;
   static int dkv_env = 5;            // round 4: version 5 (tools/gen_attn_dkv5.py); RV_ATTN_DKV=3 selects the round-2/3 kernel
-  static int dkv_ablate = 0;
-  (void)dkv_ablate;
   if (!attr_done) {
     hipFuncSetAttribute((const void*)attn_bwd_dq2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ_LDS);
     hipFuncSetAttribute((const void*)attn_bwd_dq2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ_LDS);
     hipFuncSetAttribute((const void*)attn_bwd_dkv3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS);
     hipFuncSetAttribute((const void*)attn_bwd_dkv3_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS);
-#ifdef RV_ATTN_EXPERIMENTS
-    hipFuncSetAttribute((const void*)attn_bwd_dkv3_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS);
-    hipFuncSetAttribute((const void*)attn_bwd_dkv3_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS);
-    hipFuncSetAttribute((const void*)attn_bwd_dkv3_kernel<true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS);
-    hipFuncSetAttribute((const void*)attn_bwd_dkv3_kernel<true, 5>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS);
-    hipFuncSetAttribute((const void*)attn_bwd_dkv3_kernel<true, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS);
-    { const char* a = getenv("RV_DKV_ABLATE"); if (a) dkv_ablate = atoi(a); }
-#endif
     hipFuncSetAttribute((const void*)attn_bwd_dkv5_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV5_LDS);
     hipFuncSetAttribute((const void*)attn_bwd_dkv5_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV5_LDS);
     const char* e = getenv("RV_ATTN_DKV");        // A/B knob: 3 = the round-2/3 kernel, 5 = the round-4 kernel (versions 2 and 4: history)
@@ -1744,11 +1544,6 @@ int rv_attn_bwd(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, co
     RV_CHECK_LAUNCH();
     if (dkv_version == 5)
       hipLaunchKernelGGL((attn_bwd_dkv5_kernel<true>), grid_kv, block, DKV5_LDS, st, BWD_HEAD, lse, (const float*)delta, BWD_TAIL(Hkv));
-#ifdef RV_ATTN_EXPERIMENTS
-#define RV_ABL_LAUNCH(N) else if (dkv_ablate == N) hipLaunchKernelGGL((attn_bwd_dkv3_kernel<true, N>), grid_kv, block, DKV_LDS, st, BWD_HEAD, lse, (const float*)delta, BWD_TAIL(Hkv));
-    RV_ABL_LAUNCH(1) RV_ABL_LAUNCH(2) RV_ABL_LAUNCH(3) RV_ABL_LAUNCH(5) RV_ABL_LAUNCH(6)
-#undef RV_ABL_LAUNCH
-#endif
     else
       hipLaunchKernelGGL((attn_bwd_dkv3_kernel<true>), grid_kv, block, DKV_LDS, st, BWD_HEAD, lse, (const float*)delta, BWD_TAIL(Hkv));
   } else {

@@ -118,10 +118,6 @@ __device__ __forceinline__ void fwd3_rescale(Fwd3Blk& b, float mt, bool scale_o)
   }
 }
 
-#ifndef RV_FWD3_THR
-#define RV_FWD3_THR 8.0f
-#endif
-
 // ---- VALU filler of slot SLOT of a PV phase: first part of block b's softmax.  Slots 0-3 nothing (see fwd3_unpack); slots 4-7 the
 // row maximum (the masks were applied between slots 3 and 4, the rescale decision follows slot 7), slots 8-15 exponential steps 0-7.
 template <int SLOT>
@@ -269,7 +265,7 @@ __device__ __forceinline__ void fwd3_phase_pv(const Fwd3Blk& o, Fwd3Blk& b, cons
   fwd3_pv_groups<TO, VS, 1, 2>(o.p, va, rA, rB, b, [&](auto sc) { fwd3_sm_first<decltype(sc)::value>(b, c); });
   {
     const float mt = xhalf_max(fmaxf(b.t0, b.t1)) * c;
-    if (__any(mt > b.m + RV_FWD3_THR)) fwd3_rescale<TB>(b, mt, scale_o);
+    if (__any(mt > b.m + 8.0f)) fwd3_rescale<TB>(b, mt, scale_o);      // the reference lags by more than 2^8
     b.ps0 = 0.f;
     b.ps1 = 0.f;
   }
@@ -324,7 +320,6 @@ __global__ __launch_bounds__(256, 1) void attn_fwd3_kernel(const bf16_t* __restr
 
   int blk_first, blk_second;
   pair_blocks<false, BQ>(bx, nqb, L, sh, e1, lane, CAUSAL && ((nx >> 20) & 1), CAUSAL && ((nx >> 21) & 1), blk_first, blk_second);
-  APROF_DECL            // RV_ATTN_PROF builds: +0 phase 1, +1 per-tile set-up (dispatch, DMA addresses, mask flags), +2 wait + barrier + phase 2, +3 phase 3, +4 phase 4, +5 pass prologue / epilogue
   const int npass = CAUSAL ? 2 : 1;
   for (int pass = 0; pass < npass; ++pass) {
     const int qb = (pass == 0) ? blk_first : blk_second;
@@ -386,7 +381,6 @@ __global__ __launch_bounds__(256, 1) void attn_fwd3_kernel(const bf16_t* __restr
     fwd3_phase_s<0, true, 0>(A.s, ka, B, [&](auto) {});
     asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
     fwd3_vreads<2, 0>(rA, va);                                  // group 0 of "V(-1)" (zeros x P = 0) for the first phase 1
-    APROF(5);
 
     // ---- one key tile; ST = i % 3 = the LDS stage of tile i
     auto body = [&](auto stc, int i) {
@@ -406,10 +400,8 @@ __global__ __launch_bounds__(256, 1) void attn_fwd3_kernel(const bf16_t* __restr
       }
       uint8_t* const dstk = more ? smem + SP * TILE : smem + 6 * TILE;
       uint8_t* const dstv = more ? smem + VBASE + SP * TILE : smem + 6 * TILE;
-      APROF(1);
       // phase 1: PV_B(i-1) on V(stage SP) || softmax_A(i) first part
       fwd3_phase_pv<4, SP, 0, CAUSAL>(B, A, va, rA, rB, qmA, maskA, k0 + 4 * half, c, i > 0, [&](auto) {});
-      APROF(0);
       // every wave is done with stage SP (K(i-1) since phase 2 of the last tile, V(i-1) now) -> tile i+2 may land there; and the
       // K tile of i+1 (pieces issued a whole tile ago) becomes visible to all waves for phase 4
       // (pieces are issued in EVERY tile - past the end into the scratch tile - so "all but the newest four" is always the right count)
@@ -423,14 +415,12 @@ __global__ __launch_bounds__(256, 1) void attn_fwd3_kernel(const bf16_t* __restr
         if constexpr ((sl & 3) == 1) dk.template piece<(sl >> 2)>(dstk, wave);
         if constexpr (sl == 13) fwd3_vreads<ST, 0>(rA, va);
       });
-      APROF(2);
       // phase 3: PV_A(i) on V(stage ST) || softmax_B(i) first part; K(i+1) groups 0, 1 requested at the end
       fwd3_phase_pv<0, ST, 4, CAUSAL>(A, B, va, rA, rB, qmB, maskB, k0 + 4 * half, c, i > 0, [&](auto sc) {
         constexpr int sl = decltype(sc)::value;
         if constexpr (sl == 13) fwd3_kreads<SN, 0>(ka);
         if constexpr (sl == 14) fwd3_kreads<SN, 1>(ka);
       });
-      APROF(3);
       // phase 4: S_A(i+1) from K(stage SN) || softmax_B(i) rest; V pieces of tile i+2; V(i) group 0 requested for the next phase 1
       fwd3_phase_s<0, true, SN>(A.s, ka, B, [&](auto sc) {
         constexpr int sl = decltype(sc)::value;
@@ -438,7 +428,6 @@ __global__ __launch_bounds__(256, 1) void attn_fwd3_kernel(const bf16_t* __restr
         if constexpr ((sl & 3) == 1) dv.template piece<(sl >> 2)>(dstv, wave);
         if constexpr (sl == 13) fwd3_vreads<ST, 0>(rA, va);
       });
-      APROF(4);
     };
     // One copy of the tile body per LDS stage, selected per tile (a scalar compare + branch per 2,000-cycle tile).  The first build
     // unrolled the loop three times with a two-body tail: blocks with nte % 3 == 2 then came out with garbage in the B rows of
@@ -483,7 +472,5 @@ __global__ __launch_bounds__(256, 1) void attn_fwd3_kernel(const bf16_t* __restr
     };
     store_block(std::integral_constant<int, 0>{}, qA, A.m, A.l);
     store_block(std::integral_constant<int, 4>{}, qB, B.m, B.l);
-    APROF(5);
   }  // pass
-  APROF_END(0)
 }

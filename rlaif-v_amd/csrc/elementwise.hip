@@ -1075,10 +1075,9 @@ int rv_rmsnorm_fwd_dropout(const void* x, long ldx, const int* row_idx, const vo
   return 0;
 }
 
-// workgroups (= fp32 partial rows of dw): 1024 measured best at 27 k rows (512: 278 us, 1024: 239 us, 2048: 296 us, 4096: 377 us - the partial-sum pass grows); RV_RMS_BWD_BLOCKS overrides
+// workgroups (= fp32 partial rows of dw): 1024 measured best at 27 k rows (512: 278 us, 1024: 239 us, 2048: 296 us, 4096: 377 us - the partial-sum pass grows)
 int rv_rmsnorm_bwd_nblocks(int rows) {
-  static int cap = 0;
-  if (!cap) { const char* e = getenv("RV_RMS_BWD_BLOCKS"); cap = e ? atoi(e) : 1024; if (cap < 1) cap = 1024; }
+  const int cap = 1024;
   return rows < cap ? (rows < 1 ? 1 : rows) : cap;
 }
 

@@ -25,31 +25,16 @@ static void read_group_env() {
   if (!env_done) { const char* e = getenv("RV_GEMM_GROUP"); if (e) g_group = atoi(e); env_done = true; }
 }
 
-template <class Epi, bool DMA_IN_MSEG, int ABLATE = 0, int DIST = 3, int SPLIT = 0>
+template <class Epi, bool DMA_IN_MSEG>
 static int launch_gemm256(const GemmShape& g, const Epi& epi, hipStream_t st) {
-  constexpr int LDS = (DMA_IN_MSEG ? DIST + 1 : 4) * G2_STAGE_BYTES;
+  constexpr int LDS = 4 * G2_STAGE_BYTES;
   static bool attr_done = false;
   if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_nt_256_kernel<Epi, DMA_IN_MSEG, ABLATE, DIST, SPLIT>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    hipFuncSetAttribute((const void*)gemm_nt_256_kernel<Epi, DMA_IN_MSEG>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     attr_done = true;
   }
   const int tiles_m = (g.M + G2_BM - 1) / G2_BM, tiles_n = (g.N + G2_BN - 1) / G2_BN;
-  hipLaunchKernelGGL((gemm_nt_256_kernel<Epi, DMA_IN_MSEG, ABLATE, DIST, SPLIT>), dim3(tiles_m * tiles_n), dim3(G2_THREADS),
-                     LDS, st, g, epi);
-  RV_CHECK_LAUNCH();
-  return 0;
-}
-
-template <class Epi>
-static int launch_gemm256x64(const GemmShape& g, const Epi& epi, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_nt_256x64_kernel<Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, G3_LDS_BYTES);
-    attr_done = true;
-  }
-  const int tiles_m = (g.M + G2_BM - 1) / G2_BM, tiles_n = (g.N + G2_BN - 1) / G2_BN;
-  hipLaunchKernelGGL((gemm_nt_256x64_kernel<Epi>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G3_LDS_BYTES, st, g, epi);
+  hipLaunchKernelGGL((gemm_nt_256_kernel<Epi, DMA_IN_MSEG>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), LDS, st, g, epi);
   RV_CHECK_LAUNCH();
   return 0;
 }
@@ -61,12 +46,13 @@ static int nn_mi16() {
   return g_mi16;
 }
 
-static int g_tn_dist = 3;   // prefetch distance of the TN kernel (RV_GEMM_TN_DIST = 3 | 4; measured equal, 3 = 128 KiB LDS)
-
-template <class Epi, int DIST>
-static int launch_gemm_tn_d(const bf16_t* P, long ldp, const bf16_t* Q, long ldq, int R, int I, int J, const Epi& epi,
-                            hipStream_t st, int splits, int r_chunk, long split_stride, int bid0, int nblocks) {
-  constexpr int LDS = (DIST + 1) * G2_STAGE_BYTES;
+// TN kernel: prefetch distance 3 (128 KiB LDS ring; distance 4 measured equal)
+template <class Epi>
+static int launch_gemm_tn(const bf16_t* P, long ldp, const bf16_t* Q, long ldq, int R, int I, int J, const Epi& epi,
+                          hipStream_t st, int splits = 1, int r_chunk = 0, long split_stride = 0, int bid0 = 0,
+                          int nblocks = 0) {
+  constexpr int DIST = 3, LDS = (DIST + 1) * G2_STAGE_BYTES;
+  read_group_env();
   static bool attr_done = false;
   if (!attr_done) {
     hipFuncSetAttribute((const void*)gemm_tn_256_kernel<Epi, DIST>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
@@ -85,17 +71,6 @@ static int launch_gemm_tn_d(const bf16_t* P, long ldp, const bf16_t* Q, long ldq
   return 0;
 }
 
-template <class Epi>
-static int launch_gemm_tn(const bf16_t* P, long ldp, const bf16_t* Q, long ldq, int R, int I, int J, const Epi& epi,
-                          hipStream_t st, int splits = 1, int r_chunk = 0, long split_stride = 0, int bid0 = 0,
-                          int nblocks = 0) {
-  static bool env_done = false;
-  read_group_env();
-  if (!env_done) { const char* e = getenv("RV_GEMM_TN_DIST"); if (e && atoi(e) == 4) g_tn_dist = 4; env_done = true; }
-  if (g_tn_dist == 3) return launch_gemm_tn_d<Epi, 3>(P, ldp, Q, ldq, R, I, J, epi, st, splits, r_chunk, split_stride, bid0, nblocks);
-  return launch_gemm_tn_d<Epi, 4>(P, ldp, Q, ldq, R, I, J, epi, st, splits, r_chunk, split_stride, bid0, nblocks);
-}
-
 // Tail split of a weight-gradient GEMM.  All output tiles cost the same (the contraction runs over every token), so a
 // launch of T tiles takes ceil(T / 256) rounds on 256 CUs and the last round is as long as a full one however few tiles it
 // holds (wgu: 1376 tiles = 5.375 rounds, wdown: 688 = 2.69).  (In practice a thin last round runs somewhat faster than a full
@@ -105,19 +80,12 @@ static int launch_gemm_tn(const bf16_t* P, long ldp, const bf16_t* Q, long ldq, 
 // a round instead of 1.  s = 1: no split pays (or the problem has no full round).
 struct TnTailPlan { int full_blocks, tail, splits, r_chunk; };
 static TnTailPlan tn_tail_plan(int R, int I, int J) {
-  static int enabled = -1;
-  static double penalty = 0.04;       // rounds charged per split for its fixed costs (prologue, slab store, reduce pass); measured:
+  const double penalty = 0.04;        // rounds charged per split for its fixed costs (prologue, slab store, reduce pass); measured:
                                       // 8 splits of the wgu tail gain nothing, 2 splits -2.7 % (profiles/r03_tn_tail_split.log)
-  if (enabled < 0) {
-    const char* e = getenv("RV_TN_TAIL_SPLIT");
-    enabled = e ? atoi(e) : 1;
-    const char* q = getenv("RV_TN_TAIL_PENALTY");
-    if (q) penalty = atof(q);
-  }
   const int T = ((I + 255) / 256) * ((J + 255) / 256);
   TnTailPlan p{T, 0, 1, 0};
   const int full = T / 256, tail = T % 256;
-  if (!enabled || full < 1 || tail == 0) return p;
+  if (full < 1 || tail == 0) return p;
   double best = 1.0;
   int best_s = 1;
   const int cand[5] = {2, 3, 4, 6, 8};
@@ -182,11 +150,10 @@ static int dispatch_ext(const GemmShape& g, const Epi& epi, void* stream) {
     constexpr int LDS = 4 * G2_STAGE_BYTES;
     static bool attr_done = false;
     if (!attr_done) {
-      hipFuncSetAttribute((const void*)gemm_nt_256_kernel<Epi, true, 0, 3, 0, true>,
-                          hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+      hipFuncSetAttribute((const void*)gemm_nt_256_kernel<Epi, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
       attr_done = true;
     }
-    hipLaunchKernelGGL((gemm_nt_256_kernel<Epi, true, 0, 3, 0, true>),
+    hipLaunchKernelGGL((gemm_nt_256_kernel<Epi, true, true>),
                        dim3(((g.M + G2_BM - 1) / G2_BM) * ((g.N + G2_BN - 1) / G2_BN)), dim3(G2_THREADS), LDS, st, g, epi);
     RV_CHECK_LAUNCH();
     return 0;
@@ -231,18 +198,7 @@ static int dispatch(const GemmShape& g, const Epi& epi, int variant, void* strea
     const long t256 = (long)((g.M + G2_BM - 1) / G2_BM) * ((g.N + G2_BN - 1) / G2_BN);
     variant = (t256 >= 192) ? 3 : 1;
   }
-#ifdef RV_GEMM_EXPERIMENTS
-  // Experiment builds only (rlaif-v_amd/build.py --experiments -> librlaifv_hip_exp.so): the ablations return WRONG
-  // results by construction and the schedule variants lost their A/B runs; none of them is in the shipped library.
-  if (variant == 101) return launch_gemm256<Epi, true, 1>(g, epi, (hipStream_t)stream);   // ablation: no DMA
-  if (variant == 102) return launch_gemm256<Epi, true, 2>(g, epi, (hipStream_t)stream);   // ablation: stale ds_reads
-  if (variant == 103) return launch_gemm256<Epi, true, 3>(g, epi, (hipStream_t)stream);   // ablation: L2-resident DMA
-  if (variant == 6) return launch_gemm256<Epi, true, 0, 3, 1>(g, epi, (hipStream_t)stream);
-  if (variant == 5) return launch_gemm256x64<Epi>(g, epi, (hipStream_t)stream);
-  if (variant == 4) return launch_gemm256<Epi, true, 0, 4>(g, epi, (hipStream_t)stream);
-#else
-  if (variant > 3) { rv_set_error("GEMM variant: 0..3 (experiment variants need an RV_GEMM_EXPERIMENTS build)"); return 1; }
-#endif
+  if (variant > 3) { rv_set_error("GEMM variant: 0..3"); return 1; }
   if (variant == 3) return launch_gemm256<Epi, true>(g, epi, (hipStream_t)stream);
   if (variant == 2) return launch_gemm256<Epi, false>(g, epi, (hipStream_t)stream);
   if (variant == 1) return launch_gemm<1, Epi>(g, epi, (hipStream_t)stream);
@@ -258,49 +214,9 @@ static int check_shape(const GemmShape& g, const char* who) {
   return 0;
 }
 
-#ifdef RV_GEMM_H128
-// experiment builds only: RV_H128=1 routes the NN GEMMs (plain and SwiGLU epilogues) to the two-workgroups-per-CU 128 x 256 kernel
-static unsigned* g_h128_dbg = nullptr;
-extern "C" void rv_debug_h128_dbg(unsigned* p) { g_h128_dbg = p; }
-template <class Epi>
-static bool launch_nn_h128(const GemmShape& g, const Epi& epi, hipStream_t st) {
-  static int on = -1, stagger_per_phase = 0;
-  if (on < 0) {
-    const char* e = getenv("RV_H128"); on = e ? atoi(e) : 0;
-    const char* s2 = getenv("RV_H128_STAGGER"); stagger_per_phase = s2 ? atoi(s2) : 0;     // s_memtime ticks per 32-deep phase
-  }
-  if (!on || g.K % 64 != 0 || g.K < 128) return false;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_nn_h128_kernel<Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, H128_LDS_BYTES);
-    attr_done = true;
-  }
-  const int tiles = ((g.M + 127) / 128) * ((g.N + G2_BN - 1) / G2_BN);
-  hipLaunchKernelGGL((gemm_nn_h128_kernel<Epi>), dim3(tiles), dim3(256), H128_LDS_BYTES, st, g, epi,
-                     stagger_per_phase * (g.K / G2_BK), g_h128_dbg);
-  return true;
-}
-#endif
-
-// EXPERIMENT switch (RV_GU_TILE_MAJOR=1, read once): the kept gate|up tensor of the fused SwiGLU epilogues in tile-major layout
-// (EpiSwiGLU::gu_index).  The caller must hand a buffer of ceil(M / 256) * 256 rows (rlaif-v_amd/ops.py does when the variable is
-// set); every consumer of that tensor other than rv_gemm_nn_swiglu_bwd_bf16 would read garbage - not for production use.
-static int gu_tile_major() {
-#ifdef RV_GEMM_EXPERIMENTS          // experiment library only (python rlaif-v_amd/build.py --experiments): measured, no gain - see
-  static int v = -1;               // profiles/r06_swiglu_bwd_tile_major_negative_result.log
-  if (v < 0) { const char* e = getenv("RV_GU_TILE_MAJOR"); v = (e && atoi(e) == 1) ? 1 : 0; }
-  return v;
-#else
-  return 0;
-#endif
-}
-
 // NN GEMM with one of the SwiGLU epilogues: the 64-deep-A kernel when K allows, else the 32-deep one
 template <class Epi>
 static int launch_nn_epi(const GemmShape& g, const Epi& epi, hipStream_t st) {
-#ifdef RV_GEMM_H128
-  if (launch_nn_h128(g, epi, st)) { RV_CHECK_LAUNCH(); return 0; }
-#endif
   static bool attr_done = false;
   if (!attr_done) {
     hipFuncSetAttribute((const void*)gemm_nn_256_kernel<Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES);
@@ -343,10 +259,8 @@ int rv_gemm_nt_bf16(const void* A, long lda, const void* B, long ldb, void* C, l
   GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group};
   if (check_shape(g, "rv_gemm_nt_bf16")) return 1;
   RV_REQUIRE(ldc % 4 == 0 && (residual == nullptr || ldr % 4 == 0), "rv_gemm_nt_bf16: ldc/ldr must be multiples of 4");
-  // many rows, at most 256 columns, plain store: the streaming kernel (the rank-r side of LoRA; RV_GEMM_NT_SKINNY=0: A/B knob)
-  static int skinny = -1;
-  if (skinny < 0) { const char* e = getenv("RV_GEMM_NT_SKINNY"); skinny = e ? atoi(e) : 1; }
-  if (skinny && variant < 0 && g_default_variant < 0 && N % GSK_BN == 0 && N <= 256 && M >= 4096 && bias == nullptr &&
+  // many rows, at most 256 columns, plain store: the streaming kernel (the rank-r side of LoRA)
+  if (variant < 0 && g_default_variant < 0 && N % GSK_BN == 0 && N <= 256 && M >= 4096 && bias == nullptr &&
       residual == nullptr && act == RV_ACT_NONE && ((uintptr_t)C & 7) == 0) {
     static bool attr_done = false;
     if (!attr_done) {
@@ -455,23 +369,17 @@ static int nn_bias_act(const void* A, long lda, const void* B, long ldb, void* C
   EpiStore epi{(bf16_t*)C, ldc, (const bf16_t*)bias, (const bf16_t*)residual, ldr, act, alpha};
   epi.narrow = epi_narrow();
   static bool attr_done = false;
-  static int use_a64 = 1;          // RV_GEMM_NN_A64=0: 32-deep A tiles (gemm_nn_256_kernel) also when K % 64 == 0
   if (!attr_done) {
     hipFuncSetAttribute((const void*)gemm_nn_256_kernel<EpiStore>, hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES);
     hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiStore>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
     hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiStore, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    const char* e = getenv("RV_GEMM_NN_A64");
-    if (e) use_a64 = atoi(e);
     attr_done = true;
   }
   const int tiles_m = (M + G2_BM - 1) / G2_BM, tiles_n = (N + G2_BN - 1) / G2_BN;
-#ifdef RV_GEMM_H128
-  if (launch_nn_h128(g, epi, (hipStream_t)stream)) { RV_CHECK_LAUNCH(); return 0; }
-#endif
-  if (use_a64 && K % 64 == 0 && K >= 512 && nn_mi16())
+  if (K % 64 == 0 && K >= 512 && nn_mi16())
     hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiStore, false, true>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
                        (hipStream_t)stream, g, epi);
-  else if (use_a64 && K % 64 == 0 && K >= 512)
+  else if (K % 64 == 0 && K >= 512)
     hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiStore>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
                        (hipStream_t)stream, g, epi);
   else
@@ -523,7 +431,6 @@ int rv_gemm_nn_swiglu_bf16(const void* A, long lda, const void* B, long ldb, voi
   read_group_env();
   GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group};
   EpiSwiGLU epi{(bf16_t*)GU, ldgu, (bf16_t*)ACT, ldact};
-  if (gu_tile_major()) { epi.tile_major = 1; epi.tiles_n = (N + 255) / 256; }
   return launch_nn_epi(g, epi, (hipStream_t)stream);
 }
 
@@ -538,7 +445,6 @@ int rv_gemm_nn_swiglu_bwd_bf16(const void* A, long lda, const void* B, long ldb,
   read_group_env();
   GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group};
   EpiSwiGLUBwd epi{(const bf16_t*)GU, ldgu, (bf16_t*)DGU, lddgu};
-  if (gu_tile_major()) { epi.tile_major = 1; epi.tiles_n = (2 * N + 255) / 256; }
   return launch_nn_epi(g, epi, (hipStream_t)stream);
 }
 
@@ -560,20 +466,17 @@ int rv_gemm_nn_lora_bf16(const void* A, long lda, const void* B, long ldb, const
   EpiStore epi{(bf16_t*)C, ldc, nullptr, (const bf16_t*)residual, ldr, RV_ACT_NONE, 1.0f};
   epi.narrow = epi_narrow();
   static bool attr_done = false;
-  static int use_a64 = 1;
   if (!attr_done) {
     hipFuncSetAttribute((const void*)gemm_nn_256_kernel<EpiStore, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES);
     hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiStore, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
     hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiStore, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    const char* e = getenv("RV_GEMM_NN_A64");
-    if (e) use_a64 = atoi(e);
     attr_done = true;
   }
   const int tiles_m = (M + G2_BM - 1) / G2_BM, tiles_n = (N + G2_BN - 1) / G2_BN;
-  if (use_a64 && K % 64 == 0 && K2 % 64 == 0 && K >= 512 && nn_mi16())
+  if (K % 64 == 0 && K2 % 64 == 0 && K >= 512 && nn_mi16())
     hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiStore, true, true>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
                        (hipStream_t)stream, g, epi);
-  else if (use_a64 && K % 64 == 0 && K2 % 64 == 0 && K >= 512)
+  else if (K % 64 == 0 && K2 % 64 == 0 && K >= 512)
     hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiStore, true>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
                        (hipStream_t)stream, g, epi);
   else

@@ -15,22 +15,12 @@
 
 #include "common.hpp"
 
-// Wave-priority schedule of the ping-pong kernels, measured A/B on one box (tools/exp_gemm_variants.py,
-// profiles/r02_gemm_variants_ab.log; 27,664-token step shapes):
-//   0 = s_setprio 1 around every MFMA segment, 1 = static: the second wave group at priority 1 for the whole main loop,
-//   2 = no priority changes.  TN (weight gradients): 1 beats 0 by +7.3 / +8.2 % (2: +6.3 / +6.7 %); NN: 2 beats 0 by
-//   +0.6 %, 1 loses 0.5 %.  Defaults below; -DRV_GEMM_PRIO_MODE=n forces one mode on both (experiment builds).
-//   RV_GEMM_DMA_SLOT = the MFMA slot (mod 4) after which a wave issues one LDS-DMA piece (0..3 within +-1 %: default 1).
-#ifdef RV_GEMM_PRIO_MODE
-#define RV_GEMM_PRIO_TN RV_GEMM_PRIO_MODE
-#define RV_GEMM_PRIO_NN RV_GEMM_PRIO_MODE
-#else
-#define RV_GEMM_PRIO_TN 1
-#define RV_GEMM_PRIO_NN 2
-#endif
-#ifndef RV_GEMM_DMA_SLOT
+// Wave-priority schedule of the ping-pong kernels, measured A/B on one box (profiles/r02_gemm_variants_ab.log; 27,664-token
+// step shapes), modes: 0 = s_setprio 1 around every MFMA segment, 1 = static: the second wave group at priority 1 for the whole
+// main loop, 2 = no priority changes.  TN (weight gradients): 1 beats 0 by +7.3 / +8.2 % (2: +6.3 / +6.7 %) - the TN kernel runs
+// mode 1; NN: 2 beats 0 by +0.6 %, 1 loses 0.5 % - the NN kernels run mode 2.
+// RV_GEMM_DMA_SLOT = the MFMA slot (mod 4) after which a wave issues one LDS-DMA piece (0..3 within +-1 %).
 #define RV_GEMM_DMA_SLOT 1
-#endif
 #define GEMM_BM 128
 #define GEMM_BN 128
 #define GEMM_BK 64
@@ -342,15 +332,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_skinny_kernel(GemmShape g, bf1
 // matrix pipe) instead of tile p+2 at the end of L-seg(p): the load segment shrinks to the 12 ds_reads.
 // WAR for stage (p+3)%4 = (p-1)%4: G0 issues after instance 2p = G1.Y(p-1), G1 after 2p+1 = G0.Y(p); both groups
 // retired their L-seg(p-1) reads before X(p-1).  RAW and the counted vmcnt(4) are unchanged.
-// ABLATE (debug/profiling only, results are wrong): 1 = no LDS-DMA in the main loop, 2 = no ds_reads in the loop,
-// 3 = DMA always re-reads K tile 0 (same instruction stream, every load an L2 hit).
-// DIST = prefetch distance in K tiles when DMA_IN_MSEG (ring of DIST+1 stages: 3 -> 128 KiB, 4 -> 160 KiB).
-// SPLIT = 1 (with DMA_IN_MSEG, DIST 3): pieces 0,1 of tile p+3 are issued at the end of L-seg(p), pieces 2,3 inside
-// M-seg(p) - a VMEM issue stalls the in-order wave for ~60 cycles and starves the matrix pipe, so half of them move
-// to the segment that is not using it.
-template <class Epi, bool DMA_IN_MSEG, int ABLATE = 0, int DIST = 3, int SPLIT = 0, bool EXT = false>
+// DIST = prefetch distance in K tiles when DMA_IN_MSEG (ring of DIST+1 = 4 stages, 128 KiB; a distance of 4 measured no better).
+template <class Epi, bool DMA_IN_MSEG, bool EXT = false>
 __global__ __launch_bounds__(G2_THREADS, 2) void gemm_nt_256_kernel(GemmShape g, Epi epi) {
-  constexpr int NST = DMA_IN_MSEG ? DIST + 1 : 4;
+  constexpr int DIST = 3, NST = 4;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -384,7 +369,7 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_nt_256_kernel(GemmShape g,
 
   auto issue_piece = [&](int t, int j) {   // j: 0 = A piece 0, 1 = B piece 0, 2 = A piece 1, 3 = B piece 1
     uint8_t* st = smem + (t % NST) * G2_STAGE_BYTES;
-    const long koff = (ABLATE == 3) ? 0 : (long)t * G2_BK;
+    const long koff = (long)t * G2_BK;
     const int i = j >> 1;
     if (EXT && t >= nt1) {     // wave-uniform: second K segment, addresses rebuilt on the fly (2 of ~130 steps)
       const int row = (wave * 2 + i) * 16 + (lane >> 2);
@@ -441,7 +426,6 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_nt_256_kernel(GemmShape g,
   issue(0);
   if (nt > 1) issue(1);
   if (DMA_IN_MSEG && nt > 2) issue(2);
-  if (DMA_IN_MSEG && DIST > 3 && nt > 3) issue(3);
   {
     const int issued = DMA_IN_MSEG ? min(nt, DIST) : min(nt, 2);
     if (issued >= 4) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
@@ -457,7 +441,7 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_nt_256_kernel(GemmShape g,
   // (the rolled-up form had one per DMA piece; hipcc materialised each `if (dma)` as s_cbranch + v_cndmask chains).
   auto tile = [&](const int p, auto steady_c) {
     constexpr bool STEADY = decltype(steady_c)::value;
-    const uint8_t* st = smem + ((ABLATE == 2 ? 0 : p) % NST) * G2_STAGE_BYTES;
+    const uint8_t* st = smem + (p % NST) * G2_STAGE_BYTES;
     bf16x8_t af[2][4], bfr[2][2];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
@@ -466,23 +450,13 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_nt_256_kernel(GemmShape g,
 #pragma unroll
       for (int t = 0; t < 4; ++t) af[ks][t] = *(const bf16x8_t*)(st + a_off[ks] + t * 2048);
     }
-    if (!DMA_IN_MSEG && p + 2 < nt && ABLATE != 1) issue(p + 2);
-    if (SPLIT == 1) {
-      if (p + DIST < nt) {
-        issue_piece(p + DIST, 0);
-        issue_piece(p + DIST, 1);
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // tile p+2 (4) + the two pieces just issued
-      } else if (p + 2 < nt) {
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-    } else {
+    if (!DMA_IN_MSEG && p + 2 < nt) issue(p + 2);
+    {
       // tiles newer than p+1 that are already in flight HERE (each = 4 DMA pieces of this wave): with DMA_IN_MSEG
       // tile p+DIST is only issued in the M segment that follows, so they are p+2 .. p+DIST-1; otherwise p+2.
       // (An earlier revision counted DIST-1 and thereby waited for tile p only - results then depended on the DMA
       // beating the consumer by three iterations, which a memory-bound launch mix can break.)
-      const int newer = STEADY ? DIST - 2 : ((ABLATE == 1) ? 0 : min(DMA_IN_MSEG ? DIST - 2 : 1, nt - 2 - p));
+      const int newer = STEADY ? DIST - 2 : min(DMA_IN_MSEG ? DIST - 2 : 1, nt - 2 - p);
       if (newer >= 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
       else if (newer == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       else if (newer == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -493,7 +467,7 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_nt_256_kernel(GemmShape g,
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
-    const bool dma = STEADY || (DMA_IN_MSEG && (p + DIST < nt) && ABLATE != 1);
+    const bool dma = STEADY || (DMA_IN_MSEG && (p + DIST < nt));
     // SLOT = the MFMA slot (mod 4) after which this wave issues one LDS-DMA piece (compile-time: a scalar branch
     // between MFMAs costs ~9 %, and four slot-specialised copies of the segment made hipcc spill the accumulators).
     auto mseg = [&](auto slot_c) {
@@ -506,15 +480,10 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_nt_256_kernel(GemmShape g,
           for (int tn = 0; tn < 2; ++tn) {
             acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[ks][tn], af[ks][tm], acc[tm][tn], 0, 0, 0);
             const int k = (ks * 4 + tm) * 2 + tn;
-            if (DMA_IN_MSEG && SPLIT != 1 && (k & 3) == SLOT) {
+            if (DMA_IN_MSEG && (k & 3) == SLOT) {
               __builtin_amdgcn_sched_barrier(0);
               if (STEADY && !EXT) issue_piece_run(p + DIST, k >> 2);
               else if (dma) issue_piece(p + DIST, k >> 2);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-            if (DMA_IN_MSEG && SPLIT == 1 && (k & 7) == 3) {
-              __builtin_amdgcn_sched_barrier(0);
-              if (dma) issue_piece(p + DIST, 2 + (k >> 3));
               __builtin_amdgcn_sched_barrier(0);
             }
           }
@@ -529,7 +498,7 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_nt_256_kernel(GemmShape g,
   };
   {
     int p = 0;
-    if (DMA_IN_MSEG && SPLIT == 0 && ABLATE == 0)
+    if (DMA_IN_MSEG)
       for (; p + DIST < nt; ++p) {
         tile(p, std::true_type{});
         a_run[0] += G2_BK; a_run[1] += G2_BK; b_run[0] += G2_BK; b_run[1] += G2_BK;
@@ -537,126 +506,6 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_nt_256_kernel(GemmShape g,
     for (; p < nt; ++p) tile(p, std::false_type{});
   }
   if (wm == 0) __builtin_amdgcn_s_barrier();   // re-balance the barrier count
-
-  epi.apply(*reinterpret_cast<f32x16_t(*)[2][2]>(&acc[0]), m0 + wm * 128, n0 + wn * 64, lane, g.M, g.N);
-  epi.apply(*reinterpret_cast<f32x16_t(*)[2][2]>(&acc[2]), m0 + wm * 128 + 64, n0 + wn * 64, lane, g.M, g.N);
-}
-
-// =============================================================================================
-// 256x256x64 ping-pong kernel: same two-group schedule, but a K tile is 64 deep so every LDS-DMA lane group
-// reads FULL 128-byte lines from L2 (the 32-deep tile reads half lines twice).  Two 64 KiB stages; a tile is
-// consumed in two phases (k halves); all 8 DMA pieces of tile t+1 are issued between the MFMAs of phase 2t.
-//   WAR stage (t+1)&1 (last read in phase 2t-1): G0 issues after instance 4t = G1.Y(2t-1), G1 after 4t+1.
-//   RAW tile t+1 (first read in L-seg(2t+2)): every wave drains its DMA (vmcnt(0)) before its X(2t+1).
-// =============================================================================================
-#define G3_STAGE_BYTES 65536
-#define G3_LDS_BYTES (2 * G3_STAGE_BYTES)
-
-template <class Epi>
-__global__ __launch_bounds__(G2_THREADS, 2) void gemm_nt_256x64_kernel(GemmShape g, Epi epi) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-
-  const int tiles_m = (g.M + G2_BM - 1) / G2_BM, tiles_n = (g.N + G2_BN - 1) / G2_BN;
-  const int nwg = tiles_m * tiles_n;
-  const int id = xcd_remap(blockIdx.x, nwg);
-  constexpr int GROUP = 8;
-  const int group_size = GROUP * tiles_n;
-  const int first_m = (id / group_size) * GROUP;
-  const int gsz = min(tiles_m - first_m, GROUP);
-  const int tile_m = first_m + (id % group_size) % gsz;
-  const int tile_n = (id % group_size) / gsz;
-  const int m0 = tile_m * G2_BM, n0 = tile_n * G2_BN;
-
-  // 4 pieces (1 KiB = 8 rows x 128 B) of A and of B per wave per K tile
-  const bf16_t* a_src[4];
-  const bf16_t* b_src[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = (wave * 4 + i) * 8 + (lane >> 3);
-    const int kc = (lane & 7) ^ ((row >> 1) & 7);
-    a_src[i] = g.A + (long)min(m0 + row, g.M - 1) * g.lda + kc * 8;
-    b_src[i] = g.B + (long)min(n0 + row, g.N - 1) * g.ldb + kc * 8;
-  }
-  const uint32_t piece0 = (uint32_t)(wave * 4) * 1024u;
-  auto issue_piece = [&](int t, int j) {   // j = 0..7: A piece j>>1 for even j, B piece j>>1 for odd j
-    uint8_t* st = smem + (t & 1) * G3_STAGE_BYTES;
-    const long koff = (long)t * 64;
-    const int i = j >> 1;
-    if ((j & 1) == 0)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_src[i] + koff),
-                                       (__attribute__((address_space(3))) void*)(st + piece0 + i * 1024), 16, 0, 0);
-    else
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src[i] + koff),
-                                       (__attribute__((address_space(3))) void*)(st + 32768 + piece0 + i * 1024), 16, 0, 0);
-  };
-
-  const int fr = lane & 31, half = lane >> 5;
-  uint32_t a_off[2], b_off[2];   // k-substep ks of the FIRST half tile; the second half is the same offset ^ 64
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    const uint32_t sw = (uint32_t)(((ks * 2 + half) ^ ((fr >> 1) & 7)) << 4);
-    a_off[ks] = (uint32_t)((wm * 128 + fr) * 128) + sw;
-    b_off[ks] = (uint32_t)((wn * 64 + fr) * 128) + sw + 32768u;
-  }
-
-  f32x16_t acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int nt = g.K / 64;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) issue_piece(0, j);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  if (wm == 1) __builtin_amdgcn_s_barrier();
-
-  for (int t = 0; t < nt; ++t) {
-    const uint8_t* st = smem + (t & 1) * G3_STAGE_BYTES;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      bf16x8_t af[2][4], bfr[2][2];
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) bfr[ks][u] = *(const bf16x8_t*)(st + ((b_off[ks] ^ (h * 64)) + u * 4096));
-#pragma unroll
-        for (int u = 0; u < 4; ++u) af[ks][u] = *(const bf16x8_t*)(st + ((a_off[ks] ^ (h * 64)) + u * 4096));
-      }
-      if (h == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-      const bool dma = (h == 0) && (t + 1 < nt);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-          for (int tn = 0; tn < 2; ++tn) {
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[ks][tn], af[ks][tm], acc[tm][tn], 0, 0, 0);
-            const int k = (ks * 4 + tm) * 2 + tn;
-            if (h == 0 && (k & 1) == 1) {
-              __builtin_amdgcn_sched_barrier(0);
-              if (dma) issue_piece(t + 1, k >> 1);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          }
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  if (wm == 0) __builtin_amdgcn_s_barrier();
 
   epi.apply(*reinterpret_cast<f32x16_t(*)[2][2]>(&acc[0]), m0 + wm * 128, n0 + wn * 64, lane, g.M, g.N);
   epi.apply(*reinterpret_cast<f32x16_t(*)[2][2]>(&acc[2]), m0 + wm * 128 + 64, n0 + wn * 64, lane, g.M, g.N);
@@ -698,23 +547,8 @@ __device__ __forceinline__ int acc16_elem_bits(const f32x4_t& v, int j) {
 //                                      even rows of the second): Y[p] holds a in lane bit 4;
 //   v_permlane32_swap(Y[0], Y[1])      exchanges the register bit p with lane bit 5  (upper half of the first <-> lower half of
 //                                      the second): Z[q] holds p in lane bit 5;   target register r = 8 b + 4 q + j.
-// 128 VALU swaps per wave per output tile (RV_GEMM_MI16_BPERMUTE: the ds_bpermute form above, 256 + 128 selects).
+// 128 VALU swaps per wave per output tile (the ds_bpermute form above: 256 + 128 selects).
 __device__ __forceinline__ void acc16_block_to_acc32(const f32x4_t (&a)[4][4], f32x16_t (&out)[2][2], int lane) {
-#ifdef RV_GEMM_MI16_BPERMUTE
-  const int base = (lane & 15) | ((lane >> 5) << 4);
-  const bool odd = (lane >> 4) & 1;
-#pragma unroll
-  for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-    for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int src_lane = base | (((r >> 2) & 1) << 5);
-        const int v0 = __builtin_amdgcn_ds_bpermute(src_lane << 2, acc16_elem_bits(a[2 * tm][2 * tn + (r >> 3)], r & 3));
-        const int v1 = __builtin_amdgcn_ds_bpermute(src_lane << 2, acc16_elem_bits(a[2 * tm + 1][2 * tn + (r >> 3)], r & 3));
-        out[tm][tn][r] = __builtin_bit_cast(float, odd ? v1 : v0);
-      }
-#else
   (void)lane;
   typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
 #pragma unroll
@@ -732,7 +566,6 @@ __device__ __forceinline__ void acc16_block_to_acc32(const f32x4_t (&a)[4][4], f
           out[tm][tn][8 * b + j] = __builtin_bit_cast(float, (unsigned)z[0]);
           out[tm][tn][8 * b + 4 + j] = __builtin_bit_cast(float, (unsigned)z[1]);
         }
-#endif
 }
 
 __device__ bf16_t g_zero_row[256];   // 512 zero bytes: DMA source for contraction rows beyond R
@@ -870,7 +703,7 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_tn_256_kernel(const bf16_t
   }
   __builtin_amdgcn_s_barrier();
   if (wi == 1) __builtin_amdgcn_s_barrier();
-  if (RV_GEMM_PRIO_TN == 1 && wi == 1) __builtin_amdgcn_s_setprio(1);     // wi is wave-uniform (readfirstlane)
+  if (wi == 1) __builtin_amdgcn_s_setprio(1);     // priority mode 1 (top of the file); wi is wave-uniform (readfirstlane)
 
   // STEADY tiles (all but the last DIST+1): the fetched tile p+DIST is neither past the end nor ragged, so its DMA
   // needs no validity select and no branch, and uses pointers advanced once per tile (see gemm_nt_256_kernel)
@@ -925,7 +758,6 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_tn_256_kernel(const bf16_t
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    if (RV_GEMM_PRIO_TN == 0) __builtin_amdgcn_s_setprio(1);
     const bool dma = (p + DIST < nt);
 #pragma unroll
     for (int kk = 0; kk < (MI16 ? 32 : 16); ++kk) {
@@ -945,7 +777,6 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_tn_256_kernel(const bf16_t
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    if (RV_GEMM_PRIO_TN == 0) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -1351,7 +1182,6 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_nn_a64_kernel(GemmShape g,
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    if (RV_GEMM_PRIO_NN == 0) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kk = 0; kk < (MI16 ? 32 : 16); ++kk) {
           if (MI16) {
@@ -1377,7 +1207,6 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_nn_a64_kernel(GemmShape g,
             __builtin_amdgcn_sched_barrier(0);
           }
     }
-    if (RV_GEMM_PRIO_NN == 0) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -1468,7 +1297,6 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_nn_a64_kernel(GemmShape g,
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   if (wm == 1) __builtin_amdgcn_s_barrier();   // group 1 runs one barrier behind group 0
-  if (RV_GEMM_PRIO_NN == 1 && wm == 1) __builtin_amdgcn_s_setprio(1);     // wm is wave-uniform (readfirstlane)
 
   // steady pairs: p + 4 < nt1 (A tile (p>>1)+2 and B tiles p+3, p+4 exist and lie in the main segment)
   int p = 0;
@@ -1496,169 +1324,6 @@ __global__ __launch_bounds__(G2_THREADS, 2) void gemm_nn_a64_kernel(GemmShape g,
   }
 }
 
-#ifdef RV_GEMM_H128
-// =============================================================================================
-// EXPERIMENT (-DRV_GEMM_H128 builds only): the NN GEMM as TWO 4-wave workgroups per CU on 128 x 256 tiles, so
-// that one workgroup's epilogue (the gate|up load burst + stores of the fused SwiGLU forms) can run under the other's main loop.
-// Per workgroup 80 KiB of LDS: A 2 stages x 16 KiB (128 rows x 64 deep, the A64 image), B 3 stages x 16 KiB (32 k rows x 256).
-// A wave owns 128 x 64 of the tile (the A64 kernel's strip of wave group 0) and runs ONE barrier per 32-deep phase:
-//     wait (tile data of THIS phase: counted)  ->  barrier  ->  fragment reads  ->  32 MFMAs with the DMA issues between them
-// M-seg(p) issues B tile p+2 (4 pieces per wave) and, in even phases, A tile (p>>1)+1 (4 pieces).  Hazards:
-//   RAW: phase p needs B tile p (issued in M-seg(p-2)) and A tile p>>1 (issued in M-seg(p-2) for even p, M-seg(p-3) for odd p): all
-//        but the pieces of M-seg(p-1) have landed -> vmcnt(4) in even phases (M-seg(p-1) was odd: 4 pieces), vmcnt(8) in odd
-//        ones; prologue order A0 B0 B1: vmcnt(4) in phase 0 leaves B1 in flight.
-//   WAR: B stage (p+2)%3 = (p-1)%3 and A stage ((p>>1)+1)&1 = ((p>>1)-1)&1 were last read in L-seg(p-1), which every wave has
-//        behind it when it passes barrier(p).
-// The ping-pong of the 8-wave kernels (one wave group in its MFMA segment while the other reads fragments) is left to the
-// hardware here: the two workgroups of a CU are not synchronised.  `stagger`: workgroups of the first dispatch round whose LDS
-// allocation does not start at 0 (the second one on its CU) first sleep that many s_memtime ticks, so the pair starts half a
-// tile apart.
-// =============================================================================================
-#define H128_A_STAGE 16384
-#define H128_B_STAGE 16384
-#define H128_LDS_BYTES (2 * H128_A_STAGE + 3 * H128_B_STAGE)
-template <class Epi>
-__global__ __launch_bounds__(256, 2) void gemm_nn_h128_kernel(GemmShape g, Epi epi, int stagger, unsigned* __restrict__ dbg) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint8_t* const smA = smem;
-  uint8_t* const smB = smem + 2 * H128_A_STAGE;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wn = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-  const unsigned lds_alloc = __builtin_amdgcn_s_getreg(6 | (31 << 11));        // HW_REG_LDS_ALLOC, all 32 bits
-  if (dbg && tid == 0) dbg[blockIdx.x] = lds_alloc;
-  if (stagger > 0 && (int)blockIdx.x < 2 * 256 && (lds_alloc & 0xfffu) != 0) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-    while ((long long)(__builtin_amdgcn_s_memtime() - t0) < (long long)stagger) __builtin_amdgcn_s_sleep(32);
-  }
-
-  const int tiles_m = (g.M + 127) / 128, tiles_n = (g.N + G2_BN - 1) / G2_BN;
-  const int nwg = tiles_m * tiles_n;
-  const int id = xcd_remap(blockIdx.x, nwg);
-  const int GROUP = g.group > 0 ? 2 * g.group : 8;            // the same 1024-row clusters as the 256-row kernel's GROUP 4
-  const int group_size = GROUP * tiles_n;
-  const int first_m = (id / group_size) * GROUP;
-  const int gsz = min(tiles_m - first_m, GROUP);
-  const int tile_m = first_m + (id % group_size) % gsz;
-  const int tile_n = (id % group_size) / gsz;
-  const int m0 = tile_m * 128, n0 = tile_n * G2_BN;
-  const long ldb = g.ldb;
-
-  const bf16_t* a_src[4];
-  const bf16_t* b_src[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = (wn * 4 + i) * 8 + (lane >> 3);
-    const int kc = (lane & 7) ^ ((row >> 1) & 7);
-    a_src[i] = g.A + (long)min(m0 + row, g.M - 1) * g.lda + kc * 8;
-    const int r = (wn * 4 + i) * 2 + (lane >> 5);
-    const int c = lane & 31;
-    const int slot = (c & 3) ^ (((r >> 3) & 1) << 1);
-    const int col = (((c >> 2) ^ (r & 3)) << 5) + (slot << 3);
-    b_src[i] = g.B + (long)r * ldb + min(n0 + col, g.N - 8);
-  }
-  const uint32_t piece0 = (uint32_t)(wn * 4) * 1024u;
-  auto issue_a = [&](int T, int i, const bf16_t* src) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)(smA + (T & 1) * H128_A_STAGE + piece0 + i * 1024), 16, 0, 0);
-  };
-  auto issue_b = [&](int t, int i, const bf16_t* src) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)(smB + (t % 3) * H128_B_STAGE + piece0 + i * 1024), 16, 0, 0);
-  };
-
-  const int g4 = lane >> 4, s16 = lane & 15;
-  const uint32_t a16_pre = (uint32_t)(s16 * 128) + (uint32_t)((g4 ^ (s16 >> 1)) << 4);
-  uint32_t q16[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t)
-    q16[t] = (uint32_t)((8 * g4 + (s16 >> 2)) * 512) + (uint32_t)(((wn * 2 + (t >> 1)) ^ (s16 >> 2)) << 6) +
-             (uint32_t)((((t & 1) ^ (g4 & 1)) << 5) + 8 * (s16 & 3));
-
-  f32x4_t acc16[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc16[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-  const int nt = g.K / G2_BK;                    // 32-deep phases (even: K % 64 == 0)
-  const int ntA = nt >> 1;
-  // prologue: A0 B0 B1
-#pragma unroll
-  for (int i = 0; i < 4; ++i) issue_a(0, i, a_src[i]);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) issue_b(0, i, b_src[i]);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) issue_b(1, i, b_src[i] + (long)G2_BK * ldb);
-
-  const bf16_t* a_run[4];
-  const bf16_t* b_run[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    a_run[i] = a_src[i] + (ntA > 1 ? 64 : 0);                       // A tile 1
-    b_run[i] = b_src[i] + (long)(nt > 2 ? 2 : 1) * G2_BK * ldb;      // B tile 2
-  }
-  auto phase = [&](const int p, auto hc) {
-    constexpr int H = decltype(hc)::value;                // = p & 1
-    if (H == 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    const uint8_t* stA = smA + ((p >> 1) & 1) * H128_A_STAGE;
-    const uint32_t stB = lds_addr_of(smB + (p % 3) * H128_B_STAGE);
-    const uint32_t hx = (uint32_t)H << 6;
-    bf16x8_t af[8], bfr[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) bfr[t] = ds_tr16_pair_asm(stB + q16[t], 0, 2048);
-#pragma unroll
-    for (int t = 0; t < 8; ++t) af[t] = *(const bf16x8_t*)(stA + (a16_pre ^ hx) + t * 2048);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 32; ++kk) {
-      const int tm = kk >> 2, tn = kk & 3;
-      acc16[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[tn], af[tm], acc16[tm][tn], 0, 0, 0);
-      if ((kk & 3) == 3) {                                // 8 DMA slots per phase: B pieces in slots 0..3, A pieces (even phases) in 4..7
-        const int j = kk >> 2;
-        __builtin_amdgcn_sched_barrier(0);
-        if (j < 4) issue_b((p + 2), j, b_run[j]);
-        else if (H == 0) issue_a((p >> 1) + 1, j - 4, a_run[j - 4]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
-  };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  for (int p = 0; p < nt; p += 2) {
-    // running sources of M-seg(p): B tile p+2, A tile (p>>1)+1; they stop at the last tile (redundant tail loads land in stages
-    // nobody reads any more)
-    phase(p, I0{});
-    if (p + 3 < nt) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) b_run[i] += (long)G2_BK * ldb;
-    }
-    if ((p >> 1) + 2 < ntA) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) a_run[i] += 64;
-    }
-    phase(p + 1, I1{});
-    if (p + 4 < nt) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) b_run[i] += (long)G2_BK * ldb;
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the tail loads still target this workgroup's LDS
-
-#pragma unroll
-  for (int hm = 0; hm < 2; ++hm) {
-    f32x16_t blk[2][2];
-    acc16_block_to_acc32(*reinterpret_cast<f32x4_t(*)[4][4]>(&acc16[4 * hm]), blk, lane);
-    epi.apply(blk, m0 + hm * 64, n0 + wn * 64, lane, g.M, g.N);
-  }
-}
-#endif   // RV_GEMM_H128
-
 // ---------------------------------------------------------------------------------------------
 // Epilogues.  apply() receives the wave's 64x64 accumulators and its tile origin.
 // ---------------------------------------------------------------------------------------------
@@ -1683,21 +1348,12 @@ __device__ __forceinline__ uint4 epi_pack8(const float (&f)[8]) {
 // v_permlane32_swap (upper half of the first operand <-> lower half of the second: exactly this exchange, one VALU op for
 // both outputs) instead of __shfl_xor, which hipcc lowers to ds_bpermute_b32 + two v_cndmask + an lgkmcnt wait - 64 LDS round
 // trips per wave per output tile in an epilogue nothing overlaps.  Same bits.
-#ifndef RV_EPI_PERMLANE
-#define RV_EPI_PERMLANE 1
-#endif
 __device__ __forceinline__ void epi_xhalf(float a, float b, int half, float& lo, float& hi) {
-#if RV_EPI_PERMLANE
   (void)half;
   typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
   const u32x2_t r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
   lo = __builtin_bit_cast(float, (unsigned)r[0]);
   hi = __builtin_bit_cast(float, (unsigned)r[1]);
-#else
-  const float recv = __shfl_xor(half ? a : b, 32);
-  lo = half ? recv : a;
-  hi = half ? b : recv;
-#endif
 }
 
 struct EpiStore {
@@ -1910,7 +1566,8 @@ struct EpiStoreRope {
 struct EpiSwiGLU {
   bf16_t* C; long ldc;        // gate|up, interleaved columns [M][N]
   bf16_t* ACT; long lda;      // activation [M][N/2]
-  // EXPERIMENT (round 6; RV_GU_TILE_MAJOR=1): the kept gate|up tensor TILE-MAJOR - 256 x 256 tiles, each 128 KB
+  // tile_major = 1 (round 6; measured, no gain - the launchers pass 0): the kept gate|up tensor TILE-MAJOR - 256 x 256
+  // tiles, each 128 KB
   // contiguous, tile (tm, tn) at ((tm * tiles_n + tn) << 16) - so that the backward epilogue reads two contiguous 128 KB regions
   // per output tile instead of 256 row segments 44 KB apart.  Requires a buffer of ceil(M / 256) * 256 rows.
   int tile_major = 0, tiles_n = 0;

@@ -129,8 +129,7 @@ def gemm_tn(p: torch.Tensor, q: torch.Tensor, out: Optional[torch.Tensor] = None
     return out
 
 
-_TN_WS_NEED = {}     # (R, I, J) -> floats rv_gemm_tn_workspace_floats asks for (RV_TN_TAIL_SPLIT / RV_TN_TAIL_PENALTY are read
-                     # ONCE per process, here and in the library)
+_TN_WS_NEED = {}     # (R, I, J) -> floats rv_gemm_tn_workspace_floats asks for (a pure function of the shape)
 
 
 def _lora_groups(N: int, group_cols: int, group0: int) -> int:
@@ -480,8 +479,7 @@ def linear_swiglu(x: torch.Tensor, wguT: torch.Tensor):
     N = wguT.shape[1]
     if wguT.shape[0] != K:
         raise ValueError(f"linear_swiglu: inner dimensions differ: {K} vs {wguT.shape[0]}")
-    rows = M if os.environ.get("RV_GU_TILE_MAJOR", "0") != "1" else (M + 255) // 256 * 256     # (experiment: tile-major gate|up, gemm.hip)
-    gu = torch.empty(rows, N, dtype=BF16, device=x.device)[:M]
+    gu = torch.empty(M, N, dtype=BF16, device=x.device)
     act = torch.empty(M, N // 2, dtype=BF16, device=x.device)
     hip.call("rv_gemm_nn_swiglu_bf16", x, x.stride(0), wguT, wguT.stride(0), gu, gu.stride(0), act, act.stride(0), M, N, K)
     return gu, act

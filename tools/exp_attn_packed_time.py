@@ -1,5 +1,5 @@
 """Forward and backward attention time at the bench step's packed shape (8 rows: 638 shared + 2 x 1410 tokens), for A/B runs of
-experiment libraries (RV_HIP_LIB).  Usage: [RV_HIP_LIB=...] python tools/exp_attn_packed_time.py"""
+two checkouts.  Usage: python tools/exp_attn_packed_time.py"""
 import os
 import sys
 

@@ -1,4 +1,4 @@
-"""A/B of the LDS ring depth after the vmcnt fix: NT variant 3 (DIST 3) vs 4 (DIST 4); TN via RV_GEMM_TN_DIST."""
+"""NT (variant 3) / NN GEMM times at the step's shapes (default), or the TN kernel's (argument tn)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rlaif_v_amd import ops
@@ -27,4 +27,4 @@ else:
         p = torch.randn(R, I, device="cuda").to(BF); q = torch.randn(R, J, device="cuda").to(BF); out = torch.empty(I, J, device="cuda", dtype=BF)
         for rep in range(2):
             ms = timeit(lambda: ops.gemm_tn(p, q, out=out))
-            print(f"tn dist={os.environ.get('RV_GEMM_TN_DIST','3')} {name:6s}: {ms:.3f} ms {2*R*I*J/ms/1e9:7.1f} TF/s")
+            print(f"tn {name:6s}: {ms:.3f} ms {2*R*I*J/ms/1e9:7.1f} TF/s")

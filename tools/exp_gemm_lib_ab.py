@@ -1,6 +1,6 @@
-"""One library (RV_HIP_LIB) on the step's four NN GEMM shapes: time per launch + a bit-level checksum of every output, so
-experiment builds (epilogue prefetch, sc1 / nt stores, persistent tile loop) can be compared with the shipped library for
-speed AND for identical results.  Usage: RV_HIP_LIB=... python tools/exp_gemm_lib_ab.py [--iters 8]"""
+"""The library on the step's four NN GEMM shapes: time per launch + a bit-level checksum of every output, so two checkouts
+(e.g. a kernel change and its parent) can be compared for speed AND for identical results by running this in each.
+Usage: python tools/exp_gemm_lib_ab.py [--iters 8]"""
 import argparse
 import hashlib
 import os

@@ -105,24 +105,16 @@ def body():
     s = Sched()
     s.emit("// ---- GENERATED by tools/gen_attn_dkv5.py: do not edit; the waits are counted against THIS issue order ----")
     # registers on entry (previous tile's phase IV or the loop prologue): Q_A[0..3] in AGPRs, foA[0..3], sA = -lse / scale, pA = -delta
-    s.emit("PROF(0);")
     for j in range(4):                       # lse / delta of sub-tile B first: its pre-loads run in the middle of phase I
         rl(s, 1, j)
         rd(s, 1, j)
     pf = None
     for j in range(64):
         # ------------------------------------------------------------------ in front of the MFMA
-        if j == 16:
-            s.emit("PROF(1);")
-        if j == 32:
-            s.emit("PROF(2);")
         if j == 48:
-            s.emit("PROF(3);")
             s.emit("// ---- the ONE barrier of the tile: tile t + 1 landed (this wave's pieces, then everybody's); row-read bases -> next buffer")
             s.emit("wait_all_but_newest();")
-            s.emit("PROF(5);")
             s.emit("__builtin_amdgcn_s_barrier();")
-            s.emit("PROF(6);")
             s.stmt("flip_rows();")
             pf = prefetch(s)
         if j < 32:
@@ -200,7 +192,6 @@ def body():
         if 54 <= j <= 61:                    # next tile's lse / delta, then its first row fragments: two reads per slot
             pf[j - 54]()
     s.need("FA3n")                           # the next tile starts with its first operands in registers
-    s.emit("PROF(4);")
     s.stmt("flip_tr();")
     s.emit(f"// ---- end of the generated tile body: {s.issued} LDS reads, deepest counted wait lgkmcnt({s.max_wait}) ----")
     return s

@@ -1,5 +1,5 @@
-"""Register / LDS / scratch table of the built kernels: unbundles the gfx950 code objects from rlaif-v_amd/build*/*.o and reads
-their metadata notes.  Usage: python tools/kernel_resources.py [substring] [--build build_exp]"""
+"""Register / LDS / scratch table of the built kernels: unbundles the gfx950 code objects from rlaif-v_amd/build/*.o and reads
+their metadata notes.  Usage: python tools/kernel_resources.py [substring] [--build DIR]"""
 import os
 import re
 import subprocess
