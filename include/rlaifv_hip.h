@@ -140,6 +140,31 @@ int rv_gemm_nn_lora_pre_bf16(const void* A, long lda, const void* B, long ldb, c
 int rv_gemm_tn_bf16_splitk(const void* P, long ldp, const void* Q, long ldq, void* C, long ldc, int R, int I, int J,
                            float alpha, int splits, float* workspace, void* stream);
 
+/* LoRA adapter dropout with ONE MASK PER peft MODULE (peft gives every wrapped nn.Linear its own nn.Dropout, so the G modules of a
+ * fused projection - q | k | v, gate | up - drop the same input with independent masks).  Module g uses the mask rv_dropout(p,
+ * seed_g) draws for the contiguous [rows][width] adapter input (element index row * width + col, whatever leading dimension is
+ * passed); the three functions regenerate it on the operand they hold, no dropped copy exists in memory.  G in {1, 2, 3} (seeds
+ * beyond G are ignored), rank block 64 per module, 0 <= p < 1; additive in ABI 7.
+ *
+ * Adapter down-projection: T[:, 64 g .. 64 g + 63] = alpha * dropout_{p, seed_g}(X) A_g^T, X [M][K], A [64 G][K] (stacked lora_A),
+ * T [M][64 G].  X is read once for all G modules; the kept values are scaled by 1.f / (1.f - p) and rounded to bf16 before the MFMA
+ * (rv_dropout's arithmetic); any M >= 1, K % 64 == 0; p = 0 is the plain product (K order of rv_gemm_nt_bf16). */
+int rv_gemm_nt_lora_masks_bf16(const void* X, long ldx, const void* A, long lda, void* T, long ldt, int M, int K, int G,
+                               float alpha, float p, int seed0, int seed1, int seed2, void* stream);
+
+/* Adapter term of the input gradient: C = residual + sum_g mask_{p, seed_g} o (dT_g AT_g^T) / (1 - p), dT [M][64 G], AT [N][64 G]
+ * (transposed stacked lora_A), C / residual [M][N] (residual may be NULL or C itself), masks those of the [M][N] adapter input.
+ * One read and one write of [M][N] for all modules; module g's term is added with its own rounding to bf16, i.e. the result is
+ * bit for bit that of G calls of rv_gemm_nt_dropout_bf16 with C as its own residual (G = 1 is that function).  N % 64 == 0. */
+int rv_gemm_nt_dropout_masks_bf16(const void* dT, long lddt, const void* AT, long ldat, void* C, long ldc, int M, int N, int G,
+                                  const void* residual, long ldr, float p, int seed0, int seed1, int seed2, void* stream);
+
+/* Adapter weight gradient: dA[64 g .. 64 g + 63][:] = dT_g^T dropout_{p, seed_g}(X), dT [R][64 G], X [R][K], dA [64 G][K], from
+ * one pass over X: `splits` chunks of the token rows are reduced into fp32 slabs (workspace: splits * 64 G * K floats, caller
+ * owned) which a second pass sums in a fixed order.  Deterministic.  K % 64 == 0; p = 0 is rv_gemm_tn_bf16_splitk. */
+int rv_gemm_tn_lora_masks_bf16(const void* dT, long lddt, const void* X, long ldx, void* dA, long ldda, int R, int K, int G, float p,
+                               int seed0, int seed1, int seed2, int splits, float* workspace, void* stream);
+
 /* Weight-gradient contraction over the ROW index of both operands (no transposed copies in HBM):
  *   C[i][j] = alpha * sum_r P[r][i] * Q[r][j] + residual[i][j]      P [R][I], Q [R][J], C [I][J]; I, J % 8 == 0
  * e.g. dW = dY^T X (autograd of nn.Linear); operands are transposed on the fly by ds_read_b64_tr_b16. */

@@ -235,6 +235,49 @@ static int launch_nn_epi(const GemmShape& g, const Epi& epi, hipStream_t st) {
   return 0;
 }
 
+// ---- LoRA adapter dropout with one mask per peft module (kernels: gemm.hpp "ONE MASK PER peft MODULE") ----
+static LoraMasks lora_masks(float p, int seed0, int seed1, int seed2) {
+  LoraMasks dm;
+  const int seeds[3] = {seed0, seed1, seed2};
+  for (int g = 0; g < 3; ++g) dm.key[g] = (uint32_t)seeds[g] * 0x9e3779b9u + 0x85ebca6bu;
+  dm.thresh16 = (uint32_t)((double)p * 65536.0 + 0.5);
+  dm.inv_keep = 1.f / (1.f - p);
+  return dm;
+}
+
+template <int G, int NST>
+static int launch_lora_masks_fwd(const bf16_t* X, long ldx, const bf16_t* A, long lda, bf16_t* T, long ldt, int M, int K, float alpha,
+                                 const LoraMasks& dm, hipStream_t st) {
+  constexpr int LDS = NST * (16384 + G * 8192);
+  static bool attr_done = false;
+  if (!attr_done) {
+    hipFuncSetAttribute((const void*)lora_masks_fwd_kernel<G, NST, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    hipFuncSetAttribute((const void*)lora_masks_fwd_kernel<G, NST, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    attr_done = true;
+  }
+  const dim3 grid((M + 127) / 128), block(256);
+  if (dm.thresh16) hipLaunchKernelGGL((lora_masks_fwd_kernel<G, NST, true>), grid, block, LDS, st, X, ldx, A, lda, T, ldt, M, K, alpha, dm);
+  else hipLaunchKernelGGL((lora_masks_fwd_kernel<G, NST, false>), grid, block, LDS, st, X, ldx, A, lda, T, ldt, M, K, alpha, dm);
+  RV_CHECK_LAUNCH();
+  return 0;
+}
+
+template <int G>
+static int launch_lora_masks_dgrad(const bf16_t* dT, long lddt, const bf16_t* AT, long ldat, bf16_t* C, long ldc, const bf16_t* R,
+                                   long ldr, int M, int N, const LoraMasks& dm, hipStream_t st) {
+  static bool attr_done = false;
+  if (!attr_done) {
+    hipFuncSetAttribute((const void*)lora_masks_dgrad_kernel<G, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
+    hipFuncSetAttribute((const void*)lora_masks_dgrad_kernel<G, false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
+    attr_done = true;
+  }
+  const dim3 grid(((M + GEMM_BM - 1) / GEMM_BM) * ((N + GEMM_BN - 1) / GEMM_BN)), block(GEMM_THREADS);
+  if (dm.thresh16) hipLaunchKernelGGL((lora_masks_dgrad_kernel<G, true>), grid, block, GEMM_LDS_BYTES, st, dT, lddt, AT, ldat, C, ldc, R, ldr, M, N, dm);
+  else hipLaunchKernelGGL((lora_masks_dgrad_kernel<G, false>), grid, block, GEMM_LDS_BYTES, st, dT, lddt, AT, ldat, C, ldc, R, ldr, M, N, dm);
+  RV_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" {
 
 const char* rv_last_error(void) { return g_err; }
@@ -643,6 +686,74 @@ int rv_gemm_tn_bf16_splitk(const void* P, long ldp, const void* Q, long ldq, voi
   const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, workspace, splits, I, J, alpha,
                      (bf16_t*)C, ldc);
+  RV_CHECK_LAUNCH();
+  return 0;
+}
+
+int rv_gemm_nt_lora_masks_bf16(const void* X, long ldx, const void* A, long lda, void* T, long ldt, int M, int K, int G,
+                               float alpha, float p, int seed0, int seed1, int seed2, void* stream) {
+  RV_REQUIRE(G >= 1 && G <= 3, "rv_gemm_nt_lora_masks_bf16: 1 <= G <= 3 modules");
+  RV_REQUIRE(K > 0 && K % 64 == 0, "rv_gemm_nt_lora_masks_bf16: K must be a positive multiple of 64");
+  RV_REQUIRE(p >= 0.f && p < 1.f, "rv_gemm_nt_lora_masks_bf16: 0 <= p < 1");
+  RV_REQUIRE(M >= 0 && ldx >= K && lda >= K && ldx % 8 == 0 && lda % 8 == 0 && ldt >= G * 64 && ldt % 4 == 0,
+             "rv_gemm_nt_lora_masks_bf16: bad leading dimension (ldx, lda: multiples of 8, >= K; ldt: multiple of 4, >= 64 G)");
+  if (M == 0) return 0;
+  RV_REQUIRE(X && A && T && (((uintptr_t)X | (uintptr_t)A) & 15) == 0 && ((uintptr_t)T & 7) == 0,
+             "rv_gemm_nt_lora_masks_bf16: X/A must be 16-byte aligned, T 8-byte aligned");
+  const LoraMasks dm = lora_masks(p, seed0, seed1, seed2);
+  const bf16_t *x = (const bf16_t*)X, *a = (const bf16_t*)A;
+  hipStream_t st = (hipStream_t)stream;
+  if (G == 1) return launch_lora_masks_fwd<1, 3>(x, ldx, a, lda, (bf16_t*)T, ldt, M, K, alpha, dm, st);
+  if (G == 2) return launch_lora_masks_fwd<2, 2>(x, ldx, a, lda, (bf16_t*)T, ldt, M, K, alpha, dm, st);
+  return launch_lora_masks_fwd<3, 2>(x, ldx, a, lda, (bf16_t*)T, ldt, M, K, alpha, dm, st);
+}
+
+int rv_gemm_nt_dropout_masks_bf16(const void* dT, long lddt, const void* AT, long ldat, void* C, long ldc, int M, int N, int G,
+                                  const void* residual, long ldr, float p, int seed0, int seed1, int seed2, void* stream) {
+  RV_REQUIRE(G >= 1 && G <= 3, "rv_gemm_nt_dropout_masks_bf16: 1 <= G <= 3 modules");
+  RV_REQUIRE(N > 0 && N % 64 == 0, "rv_gemm_nt_dropout_masks_bf16: N must be a positive multiple of 64");
+  RV_REQUIRE(p >= 0.f && p < 1.f, "rv_gemm_nt_dropout_masks_bf16: 0 <= p < 1");
+  RV_REQUIRE(M >= 0 && lddt >= G * 64 && ldat >= G * 64 && lddt % 8 == 0 && ldat % 8 == 0 && ldc >= N && ldc % 4 == 0 &&
+                 (residual == nullptr || (ldr >= N && ldr % 4 == 0)),
+             "rv_gemm_nt_dropout_masks_bf16: bad leading dimension (lddt, ldat: multiples of 8, >= 64 G; ldc, ldr: multiples of 4, >= N)");
+  if (M == 0) return 0;
+  RV_REQUIRE(dT && AT && C && (((uintptr_t)dT | (uintptr_t)AT) & 15) == 0 && (((uintptr_t)C | (uintptr_t)residual) & 7) == 0,
+             "rv_gemm_nt_dropout_masks_bf16: dT/AT must be 16-byte aligned, C/residual 8-byte aligned");
+  // one module: exactly rv_gemm_nt_dropout_bf16 (same kernels, same bits)
+  if (G == 1) return rv_gemm_nt_dropout_bf16(dT, lddt, AT, ldat, C, ldc, M, N, 64, residual, ldr, 1.0f, p, seed0, stream);
+  const LoraMasks dm = lora_masks(p, seed0, seed1, seed2);
+  if (G == 2)
+    return launch_lora_masks_dgrad<2>((const bf16_t*)dT, lddt, (const bf16_t*)AT, ldat, (bf16_t*)C, ldc, (const bf16_t*)residual, ldr, M, N,
+                                      dm, (hipStream_t)stream);
+  return launch_lora_masks_dgrad<3>((const bf16_t*)dT, lddt, (const bf16_t*)AT, ldat, (bf16_t*)C, ldc, (const bf16_t*)residual, ldr, M, N, dm,
+                                    (hipStream_t)stream);
+}
+
+int rv_gemm_tn_lora_masks_bf16(const void* dT, long lddt, const void* X, long ldx, void* dA, long ldda, int R, int K, int G, float p,
+                               int seed0, int seed1, int seed2, int splits, float* workspace, void* stream) {
+  RV_REQUIRE(G >= 1 && G <= 3, "rv_gemm_tn_lora_masks_bf16: 1 <= G <= 3 modules");
+  RV_REQUIRE(K > 0 && K % 64 == 0, "rv_gemm_tn_lora_masks_bf16: K must be a positive multiple of 64");
+  RV_REQUIRE(p >= 0.f && p < 1.f, "rv_gemm_tn_lora_masks_bf16: 0 <= p < 1");
+  RV_REQUIRE(R > 0 && splits >= 1 && splits <= 1024, "rv_gemm_tn_lora_masks_bf16: R > 0, 1 <= splits <= 1024");
+  RV_REQUIRE(lddt >= G * 64 && ldx >= K && lddt % 8 == 0 && ldx % 8 == 0 && ldda >= K && ldda % 4 == 0,
+             "rv_gemm_tn_lora_masks_bf16: bad leading dimension (lddt: multiple of 8, >= 64 G; ldx: multiple of 8, >= K; ldda: multiple of 4, >= K)");
+  RV_REQUIRE(dT && X && dA && (((uintptr_t)dT | (uintptr_t)X | (uintptr_t)workspace) & 15) == 0 && ((uintptr_t)dA & 7) == 0,
+             "rv_gemm_tn_lora_masks_bf16: dT/X/workspace must be 16-byte aligned, dA 8-byte aligned");
+  RV_REQUIRE(workspace != nullptr, "rv_gemm_tn_lora_masks_bf16: workspace of splits * 64 G * K floats required");
+  // p = 0: the plain split-K weight gradient
+  if (p == 0.f) return rv_gemm_tn_bf16_splitk(dT, lddt, X, ldx, dA, ldda, R, G * 64, K, 1.0f, splits, workspace, stream);
+  const int r_chunk = ((R + splits - 1) / splits + 31) / 32 * 32;
+  splits = (R + r_chunk - 1) / r_chunk;            // no empty chunk
+  const LoraMasks dm = lora_masks(p, seed0, seed1, seed2);
+  const dim3 grid((K + LMW_JT - 1) / LMW_JT, splits), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (G == 1) hipLaunchKernelGGL(lora_masks_wgrad_kernel<1>, grid, block, 0, st, (const bf16_t*)dT, lddt, (const bf16_t*)X, ldx, workspace, R, K, r_chunk, dm);
+  else if (G == 2) hipLaunchKernelGGL(lora_masks_wgrad_kernel<2>, grid, block, 0, st, (const bf16_t*)dT, lddt, (const bf16_t*)X, ldx, workspace, R, K, r_chunk, dm);
+  else hipLaunchKernelGGL(lora_masks_wgrad_kernel<3>, grid, block, 0, st, (const bf16_t*)dT, lddt, (const bf16_t*)X, ldx, workspace, R, K, r_chunk, dm);
+  RV_CHECK_LAUNCH();
+  const long n4 = (long)G * 64 * K / 4;
+  const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, workspace, splits, G * 64, K, 1.0f, (bf16_t*)dA, ldda);
   RV_CHECK_LAUNCH();
   return 0;
 }

@@ -1805,3 +1805,365 @@ struct EpiLogpBwd {
     }
   }
 };
+
+// =============================================================================================
+// LoRA adapter dropout with ONE MASK PER peft MODULE (RV_LORA_PEFT_MASKS): q / k / v (gate / up) drop the same input with
+// independent masks.  The mask is a counter hash of (seed, element index) (dropout_chunk, elementwise.hip), so the kernels that
+// consume the adapter input regenerate every module's mask on the operand they already hold - no dropped copy reaches HBM:
+//   lora_masks_fwd_kernel    T[:, 64 g ..] = alpha dropout_g(X) A_g^T       X streamed once for all G modules
+//   lora_masks_dgrad_kernel  dX = R + sum_g mask_g o (dT_g A_g) / (1 - p)   one read and one write of [M][N]
+//   lora_masks_wgrad_kernel  dA_g = dT_g^T dropout_g(X)                     X streamed once, split over the token rows
+// Module g: key[g] = uint32(seed_g) * 0x9e3779b9 + 0x85ebca6b, element index = row * width + col of the logical contiguous tensor.
+// =============================================================================================
+struct LoraMasks {
+  uint32_t key[3];
+  uint32_t thresh16;         // round(p * 65536): an element is kept iff its 16 hash bits are >= thresh16
+  float inv_keep;            // 1.f / (1.f - p)
+};
+
+// The module-independent half of dropout_chunk: 8 bf16 values times inv_keep, rounded to bf16
+__device__ __forceinline__ u32x4_t lora_scale_chunk(u32x4_t v, float inv_keep) {
+  u32x4_t o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    o[j] = pack2bf(__uint_as_float(v[j] << 16) * inv_keep, __uint_as_float(v[j] & 0xffff0000u) * inv_keep);
+  return o;
+}
+// ... and the per-module half: zero the dropped elements of 16-byte chunk i8 (= element index / 8) of the contiguous tensor
+__device__ __forceinline__ u32x4_t lora_mask_chunk(u32x4_t scaled, long i8, uint32_t thresh16, uint32_t key) {
+  const uint32_t base = (uint32_t)(i8 >> 30) * 0x9e3779b9u + key;
+  const uint32_t i4 = (uint32_t)i8 * 4u;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t h = gemm_mix32((i4 + (uint32_t)j) ^ base);
+    scaled[j] &= (((h & 0xffffu) >= thresh16) ? 0x0000ffffu : 0u) | (((h >> 16) >= thresh16) ? 0xffff0000u : 0u);
+  }
+  return scaled;
+}
+
+// T[M][G*64] = alpha * dropout_g(X[M][K]) A[G*64][K]^T.  gemm_nt_skinny_kernel with one workgroup per 128 rows computing ALL G
+// column blocks: after the ds_read of the activation fragment a lane holds one 16-byte chunk of its row, scales it once and masks
+// it once per module in front of that module's two MFMAs.  Same K order as the skinny and the 128x128 kernels.  LDS ring of NST
+// stages of 16 KB (X) + G * 8 KB (A): NST = 3 for G = 1 (72 KB), 2 for G = 2, 3 (64 / 80 KB): two workgroups per CU in every case.
+template <int G, int NST, bool DROP>
+__global__ __launch_bounds__(256, 2) void lora_masks_fwd_kernel(const bf16_t* __restrict__ X, long ldx, const bf16_t* __restrict__ A,
+                                                                long lda, bf16_t* __restrict__ T, long ldt, int M, int K, float alpha,
+                                                                LoraMasks dm) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  constexpr int STAGE = 16384 + G * 8192, PIECES = 4 + 2 * G;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int m0 = xcd_remap(blockIdx.x, (M + 127) / 128) * 128;
+
+  // DMA pieces (8 rows x 128 B): wave w owns X pieces 4w .. 4w+3 and A pieces 2G w .. 2G w + 2G - 1
+  const bf16_t* x_src[4];
+  const bf16_t* a_src[2 * G];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = (wave * 4 + i) * 8 + (lane >> 3);
+    x_src[i] = X + (long)min(m0 + row, M - 1) * ldx + (((lane & 7) ^ ((row >> 1) & 7)) << 3);
+  }
+#pragma unroll
+  for (int i = 0; i < 2 * G; ++i) {
+    const int row = (wave * 2 * G + i) * 8 + (lane >> 3);
+    a_src[i] = A + (long)row * lda + (((lane & 7) ^ ((row >> 1) & 7)) << 3);
+  }
+  auto issue = [&](int t, int stage) {
+    uint8_t* xs = smem + stage * STAGE;
+    uint8_t* as = xs + 16384;
+    const long koff = (long)t * 64;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(x_src[i] + koff),
+                                       (__attribute__((address_space(3))) void*)(xs + (wave * 4 + i) * 1024), 16, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 2 * G; ++i)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_src[i] + koff),
+                                       (__attribute__((address_space(3))) void*)(as + (wave * 2 * G + i) * 1024), 16, 0, 0);
+  };
+
+  f32x16_t acc[G][2];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[g][j][r] = 0.f;
+
+  const int nt = K / 64;
+  const int frow = lane & 31, fhalf = lane >> 5;
+  const long row8 = (long)(m0 + wave * 32 + frow) * (K >> 3);       // first chunk of this lane's row in the contiguous [M][K] tensor
+#pragma unroll
+  for (int s = 0; s < NST - 1; ++s) issue(min(s, nt - 1), s);
+  for (int t = 0; t < nt; ++t) {
+    // tile t has landed for this wave: everything but the NST - 2 newer tiles' pieces
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NST - 2) * PIECES) : "memory");
+    __builtin_amdgcn_s_barrier();        // ... and for every wave; all waves are done reading stage (t - 1) % NST
+    issue(min(t + NST - 1, nt - 1), (t + NST - 1) % NST);             // (clamped: redundant tail loads keep the count uniform)
+    const uint8_t* xs = smem + (t % NST) * STAGE;
+    const uint8_t* as = xs + 16384;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const int kc = ks * 2 + fhalf;
+      u32x4_t xv = *(const u32x4_t*)(xs + gemm_lds_off(wave * 32 + frow, kc));
+      if (DROP) xv = lora_scale_chunk(xv, dm.inv_keep);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const u32x4_t xg = DROP ? lora_mask_chunk(xv, row8 + t * 8 + kc, dm.thresh16, dm.key[g]) : xv;
+        const bf16x8_t xf = __builtin_bit_cast(bf16x8_t, xg);
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) {
+          const bf16x8_t af = *(const bf16x8_t*)(as + gemm_lds_off(g * 64 + tn * 32 + frow, kc));
+          acc[g][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, xf, acc[g][tn], 0, 0, 0);
+        }
+      }
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                // the clamped tail loads still target this workgroup's LDS
+  const int m = m0 + wave * 32 + frow;
+  if (m < M) {
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) {
+          uint2 o;
+          o.x = pack2bf(acc[g][tn][rg * 4 + 0] * alpha, acc[g][tn][rg * 4 + 1] * alpha);
+          o.y = pack2bf(acc[g][tn][rg * 4 + 2] * alpha, acc[g][tn][rg * 4 + 3] * alpha);
+          *(uint2*)(T + (long)m * ldt + g * 64 + tn * 32 + rg * 8 + 4 * fhalf) = o;
+        }
+  }
+}
+
+// dX[M][N] = R + sum_g mask_g o (dT_g AT_g^T) / (1 - p):  dT [M][G*64], AT [N][G*64] (the transposed stacked lora_A), R may be
+// null or alias dX (every element is read and written by the same lane).  gemm_nt_kernel's 128x128 tile and LDS-DMA staging; the
+// K loop has one 64-deep step per module, whose product is masked in a 16-register temporary per sub-tile and added to the running
+// value, which lives in registers as packed bf16.  Each module's term is added with its own rounding to bf16 - the arithmetic of the G launches of rv_gemm_nt_dropout_bf16
+// with dX as its own residual that this replaces, bit for bit - while [M][N] is read once and written once.
+template <int G, bool DROP>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void lora_masks_dgrad_kernel(const bf16_t* __restrict__ dT, long lddt,
+                                                                           const bf16_t* __restrict__ AT, long ldat, bf16_t* C, long ldc,
+                                                                           const bf16_t* R, long ldr, int M, int N, LoraMasks dm) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int tiles_m = (M + GEMM_BM - 1) / GEMM_BM, tiles_n = (N + GEMM_BN - 1) / GEMM_BN;
+  const int id = xcd_remap(blockIdx.x, tiles_m * tiles_n);
+  const int m0 = (id / tiles_n) * GEMM_BM, n0 = (id % tiles_n) * GEMM_BN;   // column tiles of one row block are neighbours: dT from HBM once
+
+  const bf16_t* a_src[4];
+  const bf16_t* b_src[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = wave * 32 + i * 8 + (lane >> 3);
+    const int kc = (lane & 7) ^ ((row >> 1) & 7);
+    a_src[i] = dT + (long)min(m0 + row, M - 1) * lddt + kc * 8;
+    b_src[i] = AT + (long)min(n0 + row, N - 1) * ldat + kc * 8;
+  }
+  auto issue = [&](int g, int buf) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_src[i] + g * 64),
+                                       (__attribute__((address_space(3))) void*)(smem + buf * 32768 + (wave * 4 + i) * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src[i] + g * 64),
+                                       (__attribute__((address_space(3))) void*)(smem + buf * 32768 + 16384 + (wave * 4 + i) * 1024), 16, 0, 0);
+    }
+  };
+  issue(0, 0);
+
+  const int frow = lane & 31, fhalf = lane >> 5;
+  const int mw = m0 + wm * 64, nw = n0 + wn * 64;
+  // running value, kept as the packed bf16 it is rounded to after every module: the residual (loaded while the first tiles are in
+  // flight; addresses clamped into the tensor, never stored there)
+  uint2 run[2][2][4];
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        run[tm][tn][rg] = make_uint2(0u, 0u);
+        if (R) run[tm][tn][rg] = *(const uint2*)(R + (long)min(mw + tm * 32 + frow, M - 1) * ldr + min(nw + tn * 32 + rg * 8 + 4 * fhalf, N - 4));
+      }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+#pragma unroll 1                       // (unrolled, hipcc hoists every module's hashes above the MFMAs and spills)
+  for (int g = 0; g < G; ++g) {
+    const int cur = g & 1;
+    if (g + 1 < G) issue(g + 1, cur ^ 1);
+    const uint8_t* as = smem + cur * 32768;
+    const uint8_t* bs = as + 16384;
+    f32x16_t tmp[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tmp[i][j][r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const int kc = ks * 2 + fhalf;
+      bf16x8_t af[2], bfr[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        af[t] = *(const bf16x8_t*)(as + gemm_lds_off(wm * 64 + t * 32 + frow, kc));
+        bfr[t] = *(const bf16x8_t*)(bs + gemm_lds_off(wn * 64 + t * 32 + frow, kc));
+      }
+#pragma unroll
+      for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn)
+          tmp[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bfr[tn], af[tm], tmp[tm][tn], 0, 0, 0);
+    }
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+      for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) {
+          f32x4_t v = {tmp[tm][tn][rg * 4], tmp[tm][tn][rg * 4 + 1], tmp[tm][tn][rg * 4 + 2], tmp[tm][tn][rg * 4 + 3]};
+          if (DROP) v = gemm_dropmask4(v, mw + tm * 32 + frow, nw + tn * 32 + rg * 8 + 4 * fhalf, N, dm.thresh16, dm.key[g], dm.inv_keep);
+          uint2& r = run[tm][tn][rg];
+          if (g > 0 || R != nullptr) {
+            v.x = __fadd_rn(v.x, __uint_as_float(r.x << 16)); v.y = __fadd_rn(v.y, __uint_as_float(r.x & 0xffff0000u));
+            v.z = __fadd_rn(v.z, __uint_as_float(r.y << 16)); v.w = __fadd_rn(v.w, __uint_as_float(r.y & 0xffff0000u));
+          }
+          r.x = pack2bf(v.x, v.y);
+          r.y = pack2bf(v.z, v.w);
+        }
+    if (g + 1 < G) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+  }
+#pragma unroll
+  for (int tm = 0; tm < 2; ++tm) {
+    const int m = mw + tm * 32 + frow;
+    if (m >= M) continue;
+#pragma unroll
+    for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        const int n = nw + tn * 32 + rg * 8 + 4 * fhalf;
+        if (n >= N) continue;
+        *(uint2*)(C + (long)m * ldc + n) = run[tm][tn][rg];
+      }
+  }
+}
+
+// ws[split][G*64][K] (fp32) = dT[rows of the split][G*64]^T dropout_g(X[rows of the split][K]) for the 64 rows of every module g:
+// the first pass of the split-K weight gradient (second pass: splitk_reduce_kernel, fixed order).  A workgroup owns 128 columns of
+// X and one chunk of token rows.  X is staged through registers - global load, one scaling, one mask per module, G masked copies of
+// the [32 r][128] tile written to LDS - and dT likewise; the MFMA fragments ("8 consecutive r of one column") come from
+// ds_read_b64_tr_b16 as in gemm_tn_256_kernel.  One v_mfma_f32_16x16x32_bf16 per 32-row tile and 16x16 output block, contraction
+// slot = row of the tile, tiles in order: the summation order of gemm_tn_256_kernel's default (MI16) loop, so with the same split
+// plan the result is that of rv_dropout + rv_gemm_tn_bf16_splitk per module, bit for bit.
+// LDS rows are 256 bytes (dT with G = 3: 512); the 32-byte segment sg of row r lives at segment (sg & ~7) | ((sg & 7) ^ f(r)),
+// f(r) = (r & 3) | ((r >> 3) & 1) << 2: the eight rows a half-wave's transposing read touches land in eight different segments.
+// Wave w: columns 32 w .. 32 w + 31 of the tile, all G*64 rows.
+#define LMW_JT 128
+__device__ __forceinline__ int lmw_swz(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
+template <int G>
+__global__ __launch_bounds__(256, 2) void lora_masks_wgrad_kernel(const bf16_t* __restrict__ dT, long lddt, const bf16_t* __restrict__ X,
+                                                               long ldx, float* __restrict__ ws, int R, int K, int r_chunk, LoraMasks dm) {
+  constexpr int XS = 2 * LMW_JT, TS = G <= 2 ? 256 : 512;             // bytes per LDS tile row
+  __shared__ __attribute__((aligned(16))) uint8_t xs[G][32 * XS];
+  __shared__ __attribute__((aligned(16))) uint8_t ts[32 * TS];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int j0 = blockIdx.x * LMW_JT;
+  const long r_begin = (long)blockIdx.y * r_chunk;
+  const long r_end = min((long)R, r_begin + r_chunk);
+  const int nt = (int)((r_end - r_begin + 31) / 32);
+
+  // staging: the X tile is 32 rows x 16 chunks of 16 bytes (2 per thread), the dT tile 32 rows x 8 G chunks (G per thread)
+  u32x4_t xr[2], tr[G];
+  auto load = [&](int t) {
+    const long r0 = r_begin + (long)t * 32;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = tid + i * 256, row = c >> 4, col = j0 + (c & 15) * 8;
+      xr[i] = (r0 + row < r_end && col < K) ? *(const u32x4_t*)(X + (r0 + row) * ldx + col) : u32x4_t{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+      const int c = tid + i * 256, row = c / (8 * G), ch = c % (8 * G);
+      tr[i] = (r0 + row < r_end) ? *(const u32x4_t*)(dT + (r0 + row) * lddt + ch * 8) : u32x4_t{0u, 0u, 0u, 0u};
+    }
+  };
+  auto commit = [&](int t) {
+    const long r0 = r_begin + (long)t * 32;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = tid + i * 256, row = c >> 4, ch = c & 15;
+      const long i8 = (r0 + row) * (K >> 3) + (j0 >> 3) + ch;         // chunk index in the contiguous [R][K] tensor
+      const u32x4_t sc = lora_scale_chunk(xr[i], dm.inv_keep);
+      const int off = row * XS + (((ch >> 1) ^ lmw_swz(row)) << 5) + ((ch & 1) << 4);
+#pragma unroll
+      for (int g = 0; g < G; ++g) *(u32x4_t*)(&xs[g][off]) = lora_mask_chunk(sc, i8, dm.thresh16, dm.key[g]);
+    }
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+      const int c = tid + i * 256, row = c / (8 * G), ch = c % (8 * G), sg = ch >> 1;
+      *(u32x4_t*)(&ts[row * TS + (((sg & ~7) | ((sg & 7) ^ lmw_swz(row))) << 5) + ((ch & 1) << 4)]) = tr[i];
+    }
+  };
+
+  f32x4_t acc[4 * G][2];                 // [16-row block of the module stack][16-column block of the wave's 32 columns]
+#pragma unroll
+  for (int ib = 0; ib < 4 * G; ++ib)
+#pragma unroll
+    for (int jb = 0; jb < 2; ++jb) acc[ib][jb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  // transposing reads: 16-lane group q, lane s addresses row 8 q + (s >> 2) (second read: + 4), columns 4 (s & 3) .. + 3 of a
+  // 16-column block; lane 16 q + s receives rows 8 q .. 8 q + 7 of column s = contraction slots 8 q .. 8 q + 7 of the MFMA operand
+  const int q = lane >> 4, s16 = lane & 15;
+  const int frow = 8 * q + (s16 >> 2), fswz = lmw_swz(frow);
+  uint32_t x_addr[G][2], t_addr[4 * G];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int jb = 0; jb < 2; ++jb)
+      x_addr[g][jb] = lds_addr_of(&xs[g][0]) + (uint32_t)(frow * XS + (((wave * 2 + jb) ^ fswz) << 5) + 8 * (s16 & 3));
+#pragma unroll
+  for (int ib = 0; ib < 4 * G; ++ib)
+    t_addr[ib] = lds_addr_of(&ts[0]) + (uint32_t)(frow * TS + (((ib & ~7) | ((ib & 7) ^ fswz)) << 5) + 8 * (s16 & 3));
+
+  if (nt > 0) load(0);
+  for (int t = 0; t < nt; ++t) {
+    __syncthreads();                     // every wave is done reading tile t - 1
+    commit(t);
+    __syncthreads();
+    if (t + 1 < nt) load(t + 1);         // in flight behind the MFMAs of tile t
+    bf16x8_t xf[G][2], tf[4 * G];
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int jb = 0; jb < 2; ++jb) xf[g][jb] = ds_tr16_pair_asm(x_addr[g][jb], 0, 4 * XS);
+#pragma unroll
+    for (int ib = 0; ib < 4 * G; ++ib) tf[ib] = ds_tr16_pair_asm(t_addr[ib], 0, 4 * TS);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int ib = 0; ib < 4 * G; ++ib)
+#pragma unroll
+      for (int jb = 0; jb < 2; ++jb)
+        acc[ib][jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tf[ib], xf[ib >> 2][jb], acc[ib][jb], 0, 0, 0);
+  }
+  // lane 16 q + s, register jj of block (ib, jb): row 16 ib + 4 q + jj of the module stack, column 16 jb + s of the wave's 32
+#pragma unroll
+  for (int jb = 0; jb < 2; ++jb) {
+    const int j = j0 + wave * 32 + jb * 16 + s16;
+    if (j >= K) continue;
+    float* out = ws + (long)blockIdx.y * (G * 64) * K + j;
+#pragma unroll
+    for (int ib = 0; ib < 4 * G; ++ib) {
+      out[(long)(ib * 16 + 4 * q + 0) * K] = acc[ib][jb].x;
+      out[(long)(ib * 16 + 4 * q + 1) * K] = acc[ib][jb].y;
+      out[(long)(ib * 16 + 4 * q + 2) * K] = acc[ib][jb].z;
+      out[(long)(ib * 16 + 4 * q + 3) * K] = acc[ib][jb].w;
+    }
+  }
+}

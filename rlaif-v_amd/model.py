@@ -168,8 +168,7 @@ class ParamStore:
         # Round 6: adapter models can take the fused SwiGLU epilogues too (RV_LORA_FUSE_SWIGLU=1): the frozen gate|up weight AND the
         # rows of the gate|up adapter lora_B are stored interleaved, and the fused GEMM's adapter segment runs over BOTH modules'
         # t = x A^T columns against an EXPANDED lora_B^T whose zeros keep t_gate out of the up columns (``gu_bexp``).
-        self.lora_il = lora is not None and fuse and os.environ.get("RV_LORA_FUSE_SWIGLU", "0") == "1" \
-            and os.environ.get("RV_LORA_PEFT_MASKS", "0") == "0"      # (independent gate / up masks need two adapter inputs)
+        self.lora_il = lora is not None and fuse and os.environ.get("RV_LORA_FUSE_SWIGLU", "0") == "1"
         self.interleave_gu = fuse and (lora is None or self.lora_il)
         self.gu_bexp: Dict[int, torch.Tensor] = {}      # layer -> [2 r_pad, 2 ffn] expanded transposed gate|up adapter (lora_il only)
         proj_w, proj_b = cfg.vision_param_entries()
@@ -696,15 +695,8 @@ class LlavaDPOModel:
         if self.lora is None:
             return ops.linear(x, W, st.pT(f"layers.{i}.w{grp}"), residual=residual), None, None
         if self.lora_peft_masks and self._lora_drop():
-            # one independent mask per peft module: t_g = (alpha / r) dropout_g(x) A_g^T, a skinny GEMM per module (the dropped
-            # copies are regenerated from their seeds in backward)
-            rp, A = self.lora.r_pad, st.p(f"layers.{i}.lora_{grp}.A")
-            seeds = self._module_seeds(i, grp, drop_slot)
-            t = torch.empty(x.shape[0], len(seeds) * rp, dtype=BF16, device=self.device)
-            for g, seed in enumerate(seeds):
-                xg = ops.dropout(x, self.lora.lora_dropout, seed)
-                ops.gemm_nt(xg, A[g * rp:(g + 1) * rp], out=t[:, g * rp:(g + 1) * rp], alpha=self.lora.scaling)
-                del xg
+            # one independent mask per peft module: t_g = (alpha / r) dropout_g(x) A_g^T
+            t = self._lora_t_module_masks(x, i, grp, drop_slot)
             gc, g0 = self._lora_grouping(grp)
             y = ops.linear_lora(x, W, st.pT(f"layers.{i}.w{grp}"), t, st.p(f"layers.{i}.lora_{grp}.B"),
                                 st.pT(f"layers.{i}.lora_{grp}.B"), group_cols=gc, residual=residual, group0=g0)
@@ -716,6 +708,21 @@ class LlavaDPOModel:
         y = ops.linear_lora(x, W, st.pT(f"layers.{i}.w{grp}"), t, st.p(f"layers.{i}.lora_{grp}.B"),
                             st.pT(f"layers.{i}.lora_{grp}.B"), group_cols=gc, residual=residual, group0=g0)
         return y, t, (xd if self.keep_dropped_inputs else None)
+
+    def _lora_t_module_masks(self, x: torch.Tensor, i: int, grp: str, drop_slot: int) -> torch.Tensor:
+        """t = [t_0 | .. | t_{G-1}], t_g = (alpha / r) dropout_g(x) A_g^T with one mask per peft module (RV_LORA_PEFT_MASKS): one
+        kernel that reads x once and draws every module's mask on the operand it holds (rv_gemm_nt_lora_masks_bf16).  Shapes it
+        does not serve: a dropped copy and a skinny GEMM per module."""
+        rp, A = self.lora.r_pad, self.store.p(f"layers.{i}.lora_{grp}.A")
+        seeds = self._module_seeds(i, grp, drop_slot)
+        if ops.lora_module_masks_ok(x.shape[1], rp):
+            return ops.lora_down_module_masks(x, A, self.lora.lora_dropout, seeds, alpha=self.lora.scaling)
+        t = torch.empty(x.shape[0], len(seeds) * rp, dtype=BF16, device=self.device)
+        for g, seed in enumerate(seeds):
+            xg = ops.dropout(x, self.lora.lora_dropout, seed)
+            ops.gemm_nt(xg, A[g * rp:(g + 1) * rp], out=t[:, g * rp:(g + 1) * rp], alpha=self.lora.scaling)
+            del xg
+        return t
 
     def _lora_drop(self) -> bool:
         """The adapter branch drops its input (peft lora_dropout, training mode only)."""
@@ -747,8 +754,6 @@ class LlavaDPOModel:
         BT = st.pT(bkey)                                              # [rp, total output width]
         il = grp == "gu" and st.lora_il                               # interleaved gate / up columns: the modules are column PARITIES
         if il:
-            if self.training and self.lora.lora_dropout > 0.0 and self.lora_peft_masks:
-                raise NotImplementedError("RV_LORA_FUSE_SWIGLU with RV_LORA_PEFT_MASKS")
             # dt = (alpha/r) dy bexp^T: the expanded adapter's zeros keep the gate columns of dy out of dt_up and vice versa
             dt = ops.gemm_nt(dy, st.gu_bexp[i], alpha=sc)
         else:
@@ -757,17 +762,21 @@ class LlavaDPOModel:
                 ops.gemm_nt(dy[:, c0:c0 + og], BT[:, c0:c0 + og], out=dt[:, g * rp:(g + 1) * rp], alpha=sc)
         if self.training and self.lora.lora_dropout > 0.0 and self.lora_peft_masks:
             # per-module masks: dx = dy W + sum_g mask_g * (dt_g A_g) / (1 - p); dA_g = dt_g^T dropout_g(x)
-            p_, A, AT, gA = self.lora.lora_dropout, st.p(akey), st.pT(akey), st.g(akey)
+            # (both from kernels that draw the G masks themselves: one pass over dx, one over the adapter input, no dropped copy)
+            p_, AT, gA = self.lora.lora_dropout, st.pT(akey), st.g(akey)
+            seeds = self._module_seeds(i, grp, drop_slot)
             dx = ops.linear(dy, st.pT(wkey), st.p(wkey))
-            for g, seed in enumerate(self._module_seeds(i, grp, drop_slot)):
-                dtg = dt[:, g * rp:(g + 1) * rp]
-                ops.gemm_nt_dropout(dtg, AT[:, g * rp:(g + 1) * rp], p_, seed, out=dx, residual=dx)
-                xg = ops.dropout(xin, p_, seed)
-                ops.gemm_tn_skinny(dtg, xg, out=gA[g * rp:(g + 1) * rp])
-                del xg
-            gB = st.g(bkey)
-            for g, (c0, og) in enumerate(groups):
-                ops.gemm_tn_skinny(dy[:, c0:c0 + og], t[:, g * rp:(g + 1) * rp], out=gB[c0:c0 + og])
+            if ops.lora_module_masks_ok(xin.shape[1], rp):
+                ops.lora_dgrad_module_masks(dt, AT[:, :G * rp], p_, seeds, out=dx, residual=dx)
+                ops.lora_wgrad_module_masks(dt, xin, p_, seeds, out=gA)
+            else:
+                for g, seed in enumerate(seeds):
+                    dtg = dt[:, g * rp:(g + 1) * rp]
+                    ops.gemm_nt_dropout(dtg, AT[:, g * rp:(g + 1) * rp], p_, seed, out=dx, residual=dx)
+                    xg = ops.dropout(xin, p_, seed)
+                    ops.gemm_tn_skinny(dtg, xg, out=gA[g * rp:(g + 1) * rp])
+                    del xg
+            self._lora_dB(dy, t, i, grp)
             return dx
         if self.training and self.lora.lora_dropout > 0.0:
             # dropout sits on the adapter branch only: dx = dy W + mask * (dt A) / (1 - p)
@@ -778,17 +787,22 @@ class LlavaDPOModel:
         else:
             dx = ops.linear_lora(dy, st.pT(wkey), st.p(wkey), dt, st.pT(akey), st.p(akey), group_cols=0)
         ops.gemm_tn_skinny(dt, xin, out=st.g(akey))
-        gB = st.g(bkey)
-        if il:
+        self._lora_dB(dy, t, i, grp)
+        return dx
+
+    def _lora_dB(self, dy: torch.Tensor, t: torch.Tensor, i: int, grp: str):
+        """dB_g = dy_g^T t_g of every peft module of a fused projection."""
+        st, rp = self.store, self.lora.r_pad
+        gB = st.g(f"layers.{i}.lora_{grp}.B")
+        if grp == "gu" and st.lora_il:
             # dB of both modules from ONE product dy^T [t_gate | t_up] -> [2f, 2 rp]; row 2j keeps its first rp columns (gate),
             # row 2j + 1 its last rp (up): the other halves are the cross terms the expanded adapter's zeros stand for
             full = ops.gemm_tn_skinny(dy, t)
             gB[0::2].copy_(full[0::2, :rp])
             gB[1::2].copy_(full[1::2, rp:])
-            return dx
-        for g, (c0, og) in enumerate(groups):
+            return
+        for g, (c0, og) in enumerate(lora_group_rows(self.cfg, grp)):
             ops.gemm_tn_skinny(dy[:, c0:c0 + og], t[:, g * rp:(g + 1) * rp], out=gB[c0:c0 + og])
-        return dx
 
     # ---- adapter models with interleaved gate|up layout (ParamStore.lora_il; RV_LORA_FUSE_SWIGLU=1, round 6) -----------------------
     def _lora_gu_fwd(self, xn2: torch.Tensor, i: int, xn2d: Optional[torch.Tensor], p_drop: float):
@@ -796,12 +810,15 @@ class LlavaDPOModel:
         epilogue (and the dropped activation for the down projection's adapter written by the same epilogue) at chip-filling
         shapes, the unfused composition on the same layout otherwise."""
         st, cfg = self.store, self.cfg
-        if self._lora_drop() and self.lora_peft_masks:
-            raise NotImplementedError("RV_LORA_FUSE_SWIGLU with RV_LORA_PEFT_MASKS")
         xd = xn2d
-        if xd is None and self._lora_drop():
-            xd = ops.dropout(xn2, self.lora.lora_dropout, self._dropout_seed(i, 2))
-        t = ops.gemm_nt(xn2 if xd is None else xd, st.p(f"layers.{i}.lora_gu.A"), alpha=self.lora.scaling)
+        if self._lora_drop() and self.lora_peft_masks:
+            # independent gate / up masks (seed slots 2 and 6) drawn inside the kernel that forms t = [t_gate | t_up]; the down
+            # projection's adapter input is masked the same way in its own kernel, so no dropped activation is requested (p_drop = 0)
+            t = self._lora_t_module_masks(xn2, i, "gu", 2)
+        else:
+            if xd is None and self._lora_drop():
+                xd = ops.dropout(xn2, self.lora.lora_dropout, self._dropout_seed(i, 2))
+            t = ops.gemm_nt(xn2 if xd is None else xd, st.p(f"layers.{i}.lora_gu.A"), alpha=self.lora.scaling)
         keep_xd = xd if self.keep_dropped_inputs else None
         p3, seed3 = (self.lora.lora_dropout, self._dropout_seed(i, 3)) if self._lora_drop() else (0.0, 0)
         bexp = st.gu_bexp[i]
@@ -822,8 +839,7 @@ class LlavaDPOModel:
         st, cfg = self.store, self.cfg
         rp, sc = self.lora.r_pad, self.lora.scaling
         wkey, akey, bkey = f"layers.{i}.wdown", f"layers.{i}.lora_down.A", f"layers.{i}.lora_down.B"
-        if (self.training and self.lora.lora_dropout > 0.0 and self.lora_peft_masks) or \
-                not ops.linear_lora_swiglu_ok(dy.shape[0], cfg.ffn, cfg.hidden, rp):
+        if not ops.linear_lora_swiglu_ok(dy.shape[0], cfg.ffn, cfg.hidden, rp):
             dact = self._proj_bwd(dy, act, t, i, "down", drop_slot=3, xd=xd)
             return ops.swiglu_bwd(dact, gu, interleaved=True)
         dt = ops.gemm_nt(dy, st.pT(bkey), alpha=sc)                   # dt = (alpha/r) dy B_down: [M, rp]
@@ -831,9 +847,13 @@ class LlavaDPOModel:
         p_, seed = (self.lora.lora_dropout, self._dropout_seed(i, 3)) if drop else (0.0, 0)
         dgu = ops.linear_lora_swiglu_bwd(dy, st.p(wkey), dt, st.p(akey), gu, p_, seed)
         xin = act
-        if drop:
-            xin = xd if xd is not None else ops.dropout(act, p_, seed)
-        ops.gemm_tn_skinny(dt, xin, out=st.g(akey))
+        if drop and self.lora_peft_masks and ops.lora_module_masks_ok(act.shape[1], rp):
+            # (down_proj is one peft module: its mask is the same in both modes, so the fused kernel above is exact as it is)
+            ops.lora_wgrad_module_masks(dt, act, p_, [seed], out=st.g(akey))
+        else:
+            if drop:
+                xin = xd if xd is not None else ops.dropout(act, p_, seed)
+            ops.gemm_tn_skinny(dt, xin, out=st.g(akey))
         ops.gemm_tn_skinny(dy, t, out=st.g(bkey))
         return dgu
 

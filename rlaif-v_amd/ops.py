@@ -279,6 +279,89 @@ def gemm_tn_skinny(p: torch.Tensor, q: torch.Tensor, out: Optional[torch.Tensor]
     return out
 
 
+# ---- LoRA adapter dropout with one mask per peft module (RV_LORA_PEFT_MASKS): the masks are drawn inside the adapter kernels
+def _module_seeds(seeds, who: str) -> Tuple[int, int, int]:
+    seeds = [int(s) & 0x7FFFFFFF for s in seeds]
+    if not 1 <= len(seeds) <= 3:
+        raise ValueError(f"{who}: 1 to 3 module seeds, got {len(seeds)}")
+    return tuple(seeds + [0] * (3 - len(seeds)))
+
+
+def lora_module_masks_ok(K: int, r_pad: int) -> bool:
+    """Whether the three per-module-mask kernels serve an adapter input of width K with stored rank r_pad."""
+    return K > 0 and K % 64 == 0 and r_pad == 64
+
+
+def lora_down_module_masks(x: torch.Tensor, a: torch.Tensor, p: float, seeds, alpha: float = 1.0,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """t[:, 64 g : 64 g + 64] = alpha * dropout(x; p, seeds[g]) @ a[64 g : 64 g + 64]^T for the G = len(seeds) modules stacked in
+    a [64 G, K]: x is read once, no dropped copy is written (rv_gemm_nt_lora_masks_bf16)."""
+    _chk2d(x, "x"), _chk2d(a, "a")
+    M, K = x.shape
+    G = len(seeds)
+    s = _module_seeds(seeds, "lora_down_module_masks")
+    if a.shape != (64 * G, K):
+        raise ValueError(f"lora_down_module_masks: a must be [{64 * G}, {K}] for {G} modules, got {tuple(a.shape)}")
+    if out is None:
+        out = torch.empty(M, 64 * G, dtype=BF16, device=x.device)
+    _chk2d(out, "out")
+    if out.shape != (M, 64 * G):
+        raise ValueError(f"lora_down_module_masks: out must be [{M}, {64 * G}], got {tuple(out.shape)}")
+    hip.call("rv_gemm_nt_lora_masks_bf16", x, x.stride(0), a, a.stride(0), out, out.stride(0), M, K, G, float(alpha), float(p), *s)
+    return out
+
+
+def lora_dgrad_module_masks(dt: torch.Tensor, aT: torch.Tensor, p: float, seeds, out: Optional[torch.Tensor] = None,
+                            residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = residual + sum_g dropmask(dt[:, 64 g : 64 g + 64] @ aT[:, 64 g : 64 g + 64]^T; p, seeds[g]) / (1 - p), aT [N, 64 G] the
+    transposed stacked lora_A; ``residual`` may be ``out``: one read and one write of [M, N] (rv_gemm_nt_dropout_masks_bf16)."""
+    _chk2d(dt, "dt"), _chk2d(aT, "aT")
+    M, N = dt.shape[0], aT.shape[0]
+    G = len(seeds)
+    s = _module_seeds(seeds, "lora_dgrad_module_masks")
+    if dt.shape[1] != 64 * G or aT.shape[1] != 64 * G:
+        raise ValueError(f"lora_dgrad_module_masks: dt / aT must have {64 * G} columns for {G} modules, got {tuple(dt.shape)} {tuple(aT.shape)}")
+    if out is None:
+        out = torch.empty(M, N, dtype=BF16, device=dt.device)
+    _chk2d(out, "out")
+    if residual is not None:
+        _chk2d(residual, "residual")
+    if out.shape != (M, N) or (residual is not None and residual.shape != (M, N)):
+        raise ValueError(f"lora_dgrad_module_masks: out / residual must be [{M}, {N}]")
+    hip.call("rv_gemm_nt_dropout_masks_bf16", dt, dt.stride(0), aT, aT.stride(0), out, out.stride(0), M, N, G, residual,
+             residual.stride(0) if residual is not None else 0, float(p), *s)
+    return out
+
+
+def lora_wgrad_module_masks(dt: torch.Tensor, x: torch.Tensor, p: float, seeds, out: Optional[torch.Tensor] = None,
+                            splits: int = 0) -> torch.Tensor:
+    """out[64 g : 64 g + 64] = dt[:, 64 g : 64 g + 64]^T @ dropout(x; p, seeds[g]): the stacked lora_A gradient from one pass over x,
+    split over the token rows with a deterministic fp32 second pass (rv_gemm_tn_lora_masks_bf16)."""
+    _chk2d(dt, "dt"), _chk2d(x, "x")
+    R, K = x.shape
+    G = len(seeds)
+    s = _module_seeds(seeds, "lora_wgrad_module_masks")
+    if dt.shape != (R, 64 * G):
+        raise ValueError(f"lora_wgrad_module_masks: dt must be [{R}, {64 * G}] for {G} modules, got {tuple(dt.shape)}")
+    if out is None:
+        out = torch.empty(64 * G, K, dtype=BF16, device=x.device)
+    _chk2d(out, "out")
+    if out.shape != (64 * G, K):
+        raise ValueError(f"lora_wgrad_module_masks: out must be [{64 * G}, {K}], got {tuple(out.shape)}")
+    if splits <= 0:
+        # gemm_tn_skinny's plan for ONE module's [64, K] gradient: the kernel then sums the token rows in the order of the
+        # rv_dropout + rv_gemm_tn_bf16_splitk composition it replaces (same bits), and its (K / 128) x splits workgroups fill the chip
+        splits = max(1, min(256 // ((K + 255) // 256), (R + 511) // 512))
+    key = (x.device, torch.cuda.current_stream(x.device).cuda_stream)
+    need = splits * 64 * G * K
+    ws = _SPLITK_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.float32, device=x.device)
+        _SPLITK_WS[key] = ws
+    hip.call("rv_gemm_tn_lora_masks_bf16", dt, dt.stride(0), x, x.stride(0), out, out.stride(0), R, K, G, float(p), *s, int(splits), ws)
+    return out
+
+
 def gemm_nt_f32(a, b, variant: int = -1) -> torch.Tensor:
     _chk2d(a, "a"), _chk2d(b, "b")
     out = torch.empty(a.shape[0], b.shape[0], dtype=torch.float32, device=a.device)
