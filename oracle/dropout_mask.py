@@ -66,7 +66,8 @@ def multiplier(rows: int, width: int, p: float, seed: int) -> torch.Tensor:
 
 
 def model_seed(step: int, rank: int, layer: int, slot: int) -> int:
-    """rlaif-v_amd/model.py ``LlavaDPOModel._dropout_seed``: slot 0 = q|k|v input, 1 = o input, 2 = gate|up input, 3 = down input."""
+    """rlaif-v_amd/model.py ``LlavaDPOModel._dropout_seed``: slot 0 = q|k|v input, 1 = o input, 2 = gate|up input, 3 = down input
+    (the first entries of its ``LORA_SEED_SLOTS``; restated here on purpose, not imported)."""
     return (step * 1000003 + rank * 7919 + layer * 8 + slot) & 0x7FFFFFFF
 
 
@@ -81,8 +82,8 @@ MODULE_SLOTS = {"self_attn.q_proj": 0, "self_attn.o_proj": 1, "mlp.gate_proj": 2
 def layer_masks(layer: int, rows: int, hidden: int, ffn: int, p: float, step: int = 1, rank: int = 0, per_module: bool = False):
     """{module name: multiplier [rows, in]} of one decoder layer as the HIP model draws them in its ``step``-th training forward.
     Default: q / k / v and gate / up share one mask (the fused projection drops its input once - DESIGN section 5, conscious
-    deviation).  ``per_module`` (RV_LORA_PEFT_MASKS=1, ``LlavaDPOModel._module_seeds``): every peft module its own mask, like peft's
-    one nn.Dropout per lora.Linear - k, v and up draw from the layer's spare seed slots 4, 5, 6."""
+    deviation).  ``per_module`` (RV_LORA_PEFT_MASKS=1; model.py ``LORA_SEED_SLOTS``, ``LlavaDPOModel._module_seeds``): every peft module
+    its own mask, like peft's one nn.Dropout per lora.Linear - k, v and up draw from the layer's spare seed slots 4, 5, 6."""
     out = {}
     if per_module:
         for mod, slot in MODULE_SLOTS.items():

@@ -23,7 +23,7 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -146,6 +146,22 @@ def lora_group_rows(cfg: "LlavaConfig", grp: str) -> List[Tuple[int, int]]:
     (grouped-query attention: kv_dim < hidden), gate | up are ffn each."""
     d, kvd, f = cfg.hidden, cfg.kv_dim, cfg.ffn
     return {"qkv": [(0, d), (d, kvd), (d + kvd, kvd)], "o": [(0, d)], "gu": [(0, f), (f, f)], "down": [(0, d)]}[grp]
+
+
+# fused projection -> the slots (LlavaDPOModel._dropout_seed) of its adapter dropout masks: first the one of the mask the projection
+# shares (under RV_LORA_PEFT_MASKS: of its first peft module - q, o, gate, down), then the layer's spare slots that k, v and up take then
+LORA_SEED_SLOTS = {"qkv": (0, 4, 5), "o": (1,), "gu": (2, 6), "down": (3,)}
+
+
+class LoraDrop(NamedTuple):       # the adapter-dropout mode of ONE forward and of the backward that differentiates it
+    p: float = 0.0               # peft lora_dropout in effect; 0.0 = no dropout (full fine-tune, eval mode, lora_dropout = 0)
+    per_module: bool = False     # one mask per peft module (RV_LORA_PEFT_MASKS) instead of one per fused projection
+    fused: bool = False          # the kernels that produce a projection's input also write its dropped copy
+
+
+class ProjSaved(NamedTuple):      # what an adapter projection keeps for its backward
+    t: torch.Tensor              # (alpha / r) dropout(x) A^T, the modules' blocks side by side
+    xd: Optional[torch.Tensor]   # the dropped input under a shared mask (keep_dropped_inputs), else None: regenerated from the seed
 
 
 def _is_decay(name: str) -> bool:
@@ -407,8 +423,11 @@ class LlavaDPOModel:
         self.resid_fp32 = (env != "0") if env not in (None, "") else (lora is None)
         # OPT-IN: peft's dropout semantics to the letter (RV_LORA_PEFT_MASKS=1): peft wraps every nn.Linear in its own lora.Linear with
         # its OWN nn.Dropout, so q / k / v (and gate / up) draw INDEPENDENT masks of the same input.  The default fuses them: one
-        # dropped input per fused projection (same marginals, one pass over the activation instead of three).  See _module_seeds.
+        # dropped input per fused projection (same marginals, one pass over the activation instead of three).  See LORA_SEED_SLOTS.
         self.lora_peft_masks = os.environ.get("RV_LORA_PEFT_MASKS", "0") != "0"
+        # LoRA under a shared adapter-dropout mask: the kernels that produce a projection's input also write its dropped copy (one
+        # pass less over the activation per projection; the attention output keeps the stand-alone rv_dropout)
+        self.lora_fused_dropout = os.environ.get("RV_LORA_FUSED_DROPOUT", "1") != "0"
         self.clip_fp32_resid = os.environ.get("RV_CLIP_FP32_RESID", "1") != "0"      # default ON since round 5, see clip_features
         self.fuse_rope_bwd = os.environ.get("RV_FUSE_ROPE_BWD", "1") != "0"
         self.fuse_rope_fwd = os.environ.get("RV_FUSE_ROPE_FWD", "1") != "0"      # RoPE in the q|k|v GEMM epilogue (ops.linear_rope)
@@ -685,176 +704,158 @@ class LlavaDPOModel:
             return cfg.kv_dim, (cfg.hidden if cfg.kv_dim != cfg.hidden else 0)
         return (cfg.ffn, 0) if grp == "gu" else (0, 0)
 
-    def _proj_fwd(self, x: torch.Tensor, i: int, grp: str, residual: Optional[torch.Tensor] = None,
-                  drop_slot: int = 0, xd: Optional[torch.Tensor] = None):
-        """y = x W^T (+ residual); with adapters  y = x W^T + t B^T,  t = (alpha/r) dropout(x) A^T  (peft
-        lora.Linear.forward) - the adapter term rides in the same K loop (rv_gemm_nt_lora_bf16).  Returns (y, t, xd).
-        ``xd``: dropout(x) with this slot's seed when the kernel that produced x wrote it already (_lora_drop)."""
-        st = self.store
-        W = st.p(f"layers.{i}.w{grp}")
-        if self.lora is None:
-            return ops.linear(x, W, st.pT(f"layers.{i}.w{grp}"), residual=residual), None, None
-        if self.lora_peft_masks and self._lora_drop():
-            # one independent mask per peft module: t_g = (alpha / r) dropout_g(x) A_g^T
-            t = self._lora_t_module_masks(x, i, grp, drop_slot)
-            gc, g0 = self._lora_grouping(grp)
-            y = ops.linear_lora(x, W, st.pT(f"layers.{i}.w{grp}"), t, st.p(f"layers.{i}.lora_{grp}.B"),
-                                st.pT(f"layers.{i}.lora_{grp}.B"), group_cols=gc, residual=residual, group0=g0)
-            return y, t, None
-        if xd is None and self._lora_drop():
-            xd = ops.dropout(x, self.lora.lora_dropout, self._dropout_seed(i, drop_slot))
-        t = ops.gemm_nt(x if xd is None else xd, st.p(f"layers.{i}.lora_{grp}.A"), alpha=self.lora.scaling)
-        gc, g0 = self._lora_grouping(grp)
-        y = ops.linear_lora(x, W, st.pT(f"layers.{i}.w{grp}"), t, st.p(f"layers.{i}.lora_{grp}.B"),
-                            st.pT(f"layers.{i}.lora_{grp}.B"), group_cols=gc, residual=residual, group0=g0)
-        return y, t, (xd if self.keep_dropped_inputs else None)
-
-    def _lora_t_module_masks(self, x: torch.Tensor, i: int, grp: str, drop_slot: int) -> torch.Tensor:
-        """t = [t_0 | .. | t_{G-1}], t_g = (alpha / r) dropout_g(x) A_g^T with one mask per peft module (RV_LORA_PEFT_MASKS): one
-        kernel that reads x once and draws every module's mask on the operand it holds (rv_gemm_nt_lora_masks_bf16).  Shapes it
-        does not serve: a dropped copy and a skinny GEMM per module."""
-        rp, A = self.lora.r_pad, self.store.p(f"layers.{i}.lora_{grp}.A")
-        seeds = self._module_seeds(i, grp, drop_slot)
-        if ops.lora_module_masks_ok(x.shape[1], rp):
-            return ops.lora_down_module_masks(x, A, self.lora.lora_dropout, seeds, alpha=self.lora.scaling)
-        t = torch.empty(x.shape[0], len(seeds) * rp, dtype=BF16, device=self.device)
-        for g, seed in enumerate(seeds):
-            xg = ops.dropout(x, self.lora.lora_dropout, seed)
-            ops.gemm_nt(xg, A[g * rp:(g + 1) * rp], out=t[:, g * rp:(g + 1) * rp], alpha=self.lora.scaling)
-            del xg
-        return t
-
-    def _lora_drop(self) -> bool:
-        """The adapter branch drops its input (peft lora_dropout, training mode only)."""
-        return self.lora is not None and self.training and self.lora.lora_dropout > 0.0
+    def _resolve_lora_drop(self) -> LoraDrop:
+        """The adapter-dropout mode of the forward that starts now (peft lora_dropout: adapter models in training mode only).  It travels
+        in the forward's context: backward and a checkpointed layer's re-run follow it, whatever happened to the model in between."""
+        if self.lora is None or not self.training or not self.lora.lora_dropout > 0.0:
+            return LoraDrop()
+        fused = self.lora_fused_dropout and not self.lora_peft_masks
+        if fused and self.resid_fp32:
+            raise NotImplementedError("RV_RESID_FP32 with the producer-side LoRA dropout kernels (set RV_LORA_FUSED_DROPOUT=0)")
+        return LoraDrop(self.lora.lora_dropout, self.lora_peft_masks, fused)
 
     def _dropout_seed(self, layer: int, slot: int) -> int:
         return (self._cur_drop_step * 1000003 + self.dropout_rank * 7919 + layer * 8 + slot) & 0x7FFFFFFF
 
-    def _module_seeds(self, layer: int, grp: str, slot: int) -> List[int]:
-        """RV_LORA_PEFT_MASKS: the seed of every peft module of a fused projection.  The first module keeps the fused slot's seed
-        (q: 0, o: 1, gate: 2, down: 3), the others take the layer's spare slots (k: 4, v: 5, up: 6)."""
-        extra = {"qkv": (4, 5), "gu": (6,)}.get(grp, ())
-        return [self._dropout_seed(layer, sl) for sl in (slot,) + extra]
+    def _lora_mask(self, layer: int, grp: str) -> Tuple[float, int]:
+        """(p, seed) of the mask a fused projection's adapter input shares; (0.0, 0) without dropout."""
+        p = self._cur_drop.p
+        return (p, self._dropout_seed(layer, LORA_SEED_SLOTS[grp][0])) if p else (0.0, 0)
 
-    def _proj_bwd(self, dy: torch.Tensor, xin: torch.Tensor, t: Optional[torch.Tensor], i: int, grp: str,
-                  drop_slot: int = 0, xd: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _module_seeds(self, layer: int, grp: str) -> List[int]:
+        """RV_LORA_PEFT_MASKS: the seed of every peft module of a fused projection, in stacking order."""
+        return [self._dropout_seed(layer, slot) for slot in LORA_SEED_SLOTS[grp]]
+
+    def _proj_fwd(self, x: torch.Tensor, i: int, grp: str, residual: Optional[torch.Tensor] = None, xd: Optional[torch.Tensor] = None):
+        """y = x W^T (+ residual); with adapters  y = x W^T + t B^T,  t = (alpha/r) dropout(x) A^T  (peft
+        lora.Linear.forward) - the adapter term rides in the same K loop (rv_gemm_nt_lora_bf16).  Returns (y, ProjSaved or None).
+        ``xd``: dropout(x) under the projection's shared mask when the kernel that produced x wrote it already (LoraDrop.fused)."""
+        st = self.store
+        W = st.p(f"layers.{i}.w{grp}")
+        if self.lora is None:
+            return ops.linear(x, W, st.pT(f"layers.{i}.w{grp}"), residual=residual), None
+        saved = self._lora_t(x, i, grp, xd)
+        gc, g0 = self._lora_grouping(grp)
+        y = ops.linear_lora(x, W, st.pT(f"layers.{i}.w{grp}"), saved.t, st.p(f"layers.{i}.lora_{grp}.B"),
+                            st.pT(f"layers.{i}.lora_{grp}.B"), group_cols=gc, residual=residual, group0=g0)
+        return y, saved
+
+    def _lora_t(self, x: torch.Tensor, i: int, grp: str, xd: Optional[torch.Tensor] = None) -> ProjSaved:
+        """t = [t_0 | .. | t_{G-1}], t_g = (alpha / r) dropout(x) A_g^T, of a fused projection in any dropout mode (+ what backward keeps)."""
+        drop, rp, sc = self._cur_drop, self.lora.r_pad, self.lora.scaling
+        A = self.store.p(f"layers.{i}.lora_{grp}.A")
+        if not drop.per_module:
+            if xd is None and drop.p:
+                xd = ops.dropout(x, *self._lora_mask(i, grp))
+            t = ops.gemm_nt(x if xd is None else xd, A, alpha=sc)
+            return ProjSaved(t, xd if self.keep_dropped_inputs else None)
+        # one independent mask per peft module: one kernel that reads x once and draws every module's mask on the operand it holds
+        # (rv_gemm_nt_lora_masks_bf16).  Shapes it does not serve: a dropped copy and a skinny GEMM per module.
+        seeds = self._module_seeds(i, grp)
+        if ops.lora_module_masks_ok(x.shape[1], rp):
+            return ProjSaved(ops.lora_down_module_masks(x, A, drop.p, seeds, alpha=sc), None)
+        t = torch.empty(x.shape[0], len(seeds) * rp, dtype=BF16, device=self.device)
+        for g, seed in enumerate(seeds):
+            ops.gemm_nt(ops.dropout(x, drop.p, seed), A[g * rp:(g + 1) * rp], out=t[:, g * rp:(g + 1) * rp], alpha=sc)
+        return ProjSaved(t, None)
+
+    def _proj_bwd(self, dy: torch.Tensor, xin: torch.Tensor, saved: Optional[ProjSaved], i: int, grp: str) -> torch.Tensor:
         """Input gradient of _proj_fwd; writes the weight gradients that exist (full fine-tune: dW = dy^T x by the TN
         GEMM; LoRA: dA = dt^T x_d, dB = dy^T t by the split-K TN GEMM, base weight frozen)."""
         st = self.store
-        wkey = f"layers.{i}.w{grp}"
+        wkey, akey = f"layers.{i}.w{grp}", f"layers.{i}.lora_{grp}.A"
         if self.lora is None:
             dx = ops.linear(dy, st.pT(wkey), st.p(wkey))        # dx = dy @ W: "weight" = W^T, its transpose = W itself
             ops.gemm_tn(dy, xin, out=st.g(wkey))
             return dx
-        rp, sc = self.lora.r_pad, self.lora.scaling
-        akey, bkey = f"layers.{i}.lora_{grp}.A", f"layers.{i}.lora_{grp}.B"
-        groups = lora_group_rows(self.cfg, grp)                       # (first output column, width) per peft module
-        G = len(groups)
-        BT = st.pT(bkey)                                              # [rp, total output width]
-        il = grp == "gu" and st.lora_il                               # interleaved gate / up columns: the modules are column PARITIES
-        if il:
-            # dt = (alpha/r) dy bexp^T: the expanded adapter's zeros keep the gate columns of dy out of dt_up and vice versa
-            dt = ops.gemm_nt(dy, st.gu_bexp[i], alpha=sc)
-        else:
-            dt = torch.empty(dy.shape[0], G * rp, dtype=BF16, device=self.device)
-            for g, (c0, og) in enumerate(groups):                     # dt_g = (alpha/r) dy_g B_g
-                ops.gemm_nt(dy[:, c0:c0 + og], BT[:, c0:c0 + og], out=dt[:, g * rp:(g + 1) * rp], alpha=sc)
-        if self.training and self.lora.lora_dropout > 0.0 and self.lora_peft_masks:
-            # per-module masks: dx = dy W + sum_g mask_g * (dt_g A_g) / (1 - p); dA_g = dt_g^T dropout_g(x)
-            # (both from kernels that draw the G masks themselves: one pass over dx, one over the adapter input, no dropped copy)
-            p_, AT, gA = self.lora.lora_dropout, st.pT(akey), st.g(akey)
-            seeds = self._module_seeds(i, grp, drop_slot)
+        drop = self._cur_drop
+        dt = self._lora_dt(dy, i, grp)
+        if drop.per_module:
+            # dx = dy W + sum_g mask_g * (dt_g A_g) / (1 - p): _lora_wgrads adds the adapter terms, next to the dA that shares their masks
             dx = ops.linear(dy, st.pT(wkey), st.p(wkey))
+        elif drop.p:
+            # dropout sits on the adapter branch only: dx = dy W + mask * (dt A) / (1 - p)
+            dx = ops.lora_dgrad_dropout(dy, st.p(wkey), st.pT(wkey), dt, st.p(akey), st.pT(akey), *self._lora_mask(i, grp))
+        else:
+            dx = ops.linear_lora(dy, st.pT(wkey), st.p(wkey), dt, st.pT(akey), st.p(akey), group_cols=0)
+        self._lora_wgrads(dy, dt, xin, saved, i, grp, dx=dx if drop.per_module else None)
+        return dx
+
+    def _lora_dt(self, dy: torch.Tensor, i: int, grp: str) -> torch.Tensor:
+        """dt = [dt_0 | .. | dt_{G-1}], dt_g = (alpha / r) dy_g B_g: the gradient of _lora_t's t."""
+        st, rp, sc = self.store, self.lora.r_pad, self.lora.scaling
+        if grp == "gu" and st.lora_il:
+            # interleaved gate / up columns, the modules are column PARITIES: dt = (alpha/r) dy bexp^T, the expanded adapter's zeros
+            # keep the gate columns of dy out of dt_up and vice versa
+            return ops.gemm_nt(dy, st.gu_bexp[i], alpha=sc)
+        groups = lora_group_rows(self.cfg, grp)                       # (first output column, width) per peft module
+        BT = st.pT(f"layers.{i}.lora_{grp}.B")                        # [rp, total output width]
+        dt = torch.empty(dy.shape[0], len(groups) * rp, dtype=BF16, device=self.device)
+        for g, (c0, og) in enumerate(groups):
+            ops.gemm_nt(dy[:, c0:c0 + og], BT[:, c0:c0 + og], out=dt[:, g * rp:(g + 1) * rp], alpha=sc)
+        return dt
+
+    def _lora_wgrads(self, dy: torch.Tensor, dt: torch.Tensor, xin: torch.Tensor, saved: ProjSaved, i: int, grp: str,
+                     dx: Optional[torch.Tensor] = None):
+        """The adapter weight gradients of a fused projection in any dropout mode and either gate|up layout: dA_g = dt_g^T dropout_g(x),
+        dB_g = dy_g^T t_g.  ``dx`` (per-module masks, where the caller's input gradient holds dy W only so far): the adapter terms
+        sum_g mask_g * (dt_g A_g) / (1 - p) are added to it here, from the same seeds."""
+        st, rp, drop = self.store, self.lora.r_pad, self._cur_drop
+        gA, gB = st.g(f"layers.{i}.lora_{grp}.A"), st.g(f"layers.{i}.lora_{grp}.B")
+        if not drop.per_module:
+            if drop.p:
+                # the dropped adapter input: kept from forward (288 GB HBM) or regenerated from the seed
+                xin = saved.xd if saved.xd is not None else ops.dropout(xin, *self._lora_mask(i, grp))
+            ops.gemm_tn_skinny(dt, xin, out=gA)
+        else:
+            # both from kernels that draw the G masks themselves: one pass over dx, one over the adapter input, no dropped copy
+            seeds, AT = self._module_seeds(i, grp), st.pT(f"layers.{i}.lora_{grp}.A")
             if ops.lora_module_masks_ok(xin.shape[1], rp):
-                ops.lora_dgrad_module_masks(dt, AT[:, :G * rp], p_, seeds, out=dx, residual=dx)
-                ops.lora_wgrad_module_masks(dt, xin, p_, seeds, out=gA)
+                if dx is not None:
+                    ops.lora_dgrad_module_masks(dt, AT[:, :len(seeds) * rp], drop.p, seeds, out=dx, residual=dx)
+                ops.lora_wgrad_module_masks(dt, xin, drop.p, seeds, out=gA)
             else:
                 for g, seed in enumerate(seeds):
                     dtg = dt[:, g * rp:(g + 1) * rp]
-                    ops.gemm_nt_dropout(dtg, AT[:, g * rp:(g + 1) * rp], p_, seed, out=dx, residual=dx)
-                    xg = ops.dropout(xin, p_, seed)
-                    ops.gemm_tn_skinny(dtg, xg, out=gA[g * rp:(g + 1) * rp])
-                    del xg
-            self._lora_dB(dy, t, i, grp)
-            return dx
-        if self.training and self.lora.lora_dropout > 0.0:
-            # dropout sits on the adapter branch only: dx = dy W + mask * (dt A) / (1 - p)
-            dx = ops.lora_dgrad_dropout(dy, st.p(wkey), st.pT(wkey), dt, st.p(akey), st.pT(akey), self.lora.lora_dropout,
-                                        self._dropout_seed(i, drop_slot))
-            # the dropped adapter input: kept from forward (288 GB HBM) or regenerated from the seed
-            xin = xd if xd is not None else ops.dropout(xin, self.lora.lora_dropout, self._dropout_seed(i, drop_slot))
-        else:
-            dx = ops.linear_lora(dy, st.pT(wkey), st.p(wkey), dt, st.pT(akey), st.p(akey), group_cols=0)
-        ops.gemm_tn_skinny(dt, xin, out=st.g(akey))
-        self._lora_dB(dy, t, i, grp)
-        return dx
-
-    def _lora_dB(self, dy: torch.Tensor, t: torch.Tensor, i: int, grp: str):
-        """dB_g = dy_g^T t_g of every peft module of a fused projection."""
-        st, rp = self.store, self.lora.r_pad
-        gB = st.g(f"layers.{i}.lora_{grp}.B")
+                    if dx is not None:
+                        ops.gemm_nt_dropout(dtg, AT[:, g * rp:(g + 1) * rp], drop.p, seed, out=dx, residual=dx)
+                    ops.gemm_tn_skinny(dtg, ops.dropout(xin, drop.p, seed), out=gA[g * rp:(g + 1) * rp])
         if grp == "gu" and st.lora_il:
             # dB of both modules from ONE product dy^T [t_gate | t_up] -> [2f, 2 rp]; row 2j keeps its first rp columns (gate),
             # row 2j + 1 its last rp (up): the other halves are the cross terms the expanded adapter's zeros stand for
-            full = ops.gemm_tn_skinny(dy, t)
+            full = ops.gemm_tn_skinny(dy, saved.t)
             gB[0::2].copy_(full[0::2, :rp])
             gB[1::2].copy_(full[1::2, rp:])
-            return
-        for g, (c0, og) in enumerate(lora_group_rows(self.cfg, grp)):
-            ops.gemm_tn_skinny(dy[:, c0:c0 + og], t[:, g * rp:(g + 1) * rp], out=gB[c0:c0 + og])
+        else:
+            for g, (c0, og) in enumerate(lora_group_rows(self.cfg, grp)):
+                ops.gemm_tn_skinny(dy[:, c0:c0 + og], saved.t[:, g * rp:(g + 1) * rp], out=gB[c0:c0 + og])
 
     # ---- adapter models with interleaved gate|up layout (ParamStore.lora_il; RV_LORA_FUSE_SWIGLU=1, round 6) -----------------------
-    def _lora_gu_fwd(self, xn2: torch.Tensor, i: int, xn2d: Optional[torch.Tensor], p_drop: float):
-        """(gu, act, actd, t, xd) of the gate|up projection + SwiGLU of an adapter model: the fused-LoRA GEMM with the SwiGLU
+    def _lora_gu_fwd(self, xn2: torch.Tensor, i: int, xn2d: Optional[torch.Tensor]):
+        """(gu, act, actd, ProjSaved) of the gate|up projection + SwiGLU of an adapter model: the fused-LoRA GEMM with the SwiGLU
         epilogue (and the dropped activation for the down projection's adapter written by the same epilogue) at chip-filling
         shapes, the unfused composition on the same layout otherwise."""
         st, cfg = self.store, self.cfg
-        xd = xn2d
-        if self._lora_drop() and self.lora_peft_masks:
-            # independent gate / up masks (seed slots 2 and 6) drawn inside the kernel that forms t = [t_gate | t_up]; the down
-            # projection's adapter input is masked the same way in its own kernel, so no dropped activation is requested (p_drop = 0)
-            t = self._lora_t_module_masks(xn2, i, "gu", 2)
-        else:
-            if xd is None and self._lora_drop():
-                xd = ops.dropout(xn2, self.lora.lora_dropout, self._dropout_seed(i, 2))
-            t = ops.gemm_nt(xn2 if xd is None else xd, st.p(f"layers.{i}.lora_gu.A"), alpha=self.lora.scaling)
-        keep_xd = xd if self.keep_dropped_inputs else None
-        p3, seed3 = (self.lora.lora_dropout, self._dropout_seed(i, 3)) if self._lora_drop() else (0.0, 0)
-        bexp = st.gu_bexp[i]
+        saved = self._lora_t(xn2, i, "gu", xn2d)
+        # the producer-side dropped copy only when the fused-dropout path wants it, as swiglu_fwd_dropout does (per-module masks: the
+        # down projection's adapter input is masked in its own kernel, so none is requested)
+        fused, (p3, seed3), bexp = self._cur_drop.fused, self._lora_mask(i, "down"), st.gu_bexp[i]
         if ops.linear_lora_swiglu_ok(xn2.shape[0], cfg.ffn, cfg.hidden, self.lora.r_pad):
-            # the producer-side dropped copy only when the fused-dropout path wants it (p_drop > 0), as swiglu_fwd_dropout does
-            gu, act, actd = ops.linear_lora_swiglu(xn2, st.pT(f"layers.{i}.wgu"), t, bexp, p3 if p_drop > 0.0 else 0.0, seed3)
-            return gu, act, actd, t, keep_xd
+            return ops.linear_lora_swiglu(xn2, st.pT(f"layers.{i}.wgu"), saved.t, bexp, p3 if fused else 0.0, seed3) + (saved,)
         gu = ops.linear(xn2, st.p(f"layers.{i}.wgu"), st.pT(f"layers.{i}.wgu"))
-        ops.gemm_nn(t, bexp, out=gu, residual=gu)
+        ops.gemm_nn(saved.t, bexp, out=gu, residual=gu)
         act = ops.swiglu_fwd(gu, interleaved=True)
-        actd = ops.dropout(act, p3, seed3) if p_drop > 0.0 else None
-        return gu, act, actd, t, keep_xd
+        return gu, act, (ops.dropout(act, p3, seed3) if fused else None), saved
 
-    def _lora_down_bwd_swiglu(self, dy: torch.Tensor, act: torch.Tensor, t: torch.Tensor, i: int, xd: Optional[torch.Tensor],
-                              gu: torch.Tensor) -> torch.Tensor:
+    def _lora_down_bwd_swiglu(self, dy: torch.Tensor, act: torch.Tensor, saved: ProjSaved, i: int, gu: torch.Tensor) -> torch.Tensor:
         """d(gate|up) of an adapter model: the down projection's backward (_proj_bwd "down": dA, dB, input gradient) with the SwiGLU
-        backward in the epilogue of its input-gradient GEMM."""
-        st, cfg = self.store, self.cfg
-        rp, sc = self.lora.r_pad, self.lora.scaling
-        wkey, akey, bkey = f"layers.{i}.wdown", f"layers.{i}.lora_down.A", f"layers.{i}.lora_down.B"
-        if not ops.linear_lora_swiglu_ok(dy.shape[0], cfg.ffn, cfg.hidden, rp):
-            dact = self._proj_bwd(dy, act, t, i, "down", drop_slot=3, xd=xd)
-            return ops.swiglu_bwd(dact, gu, interleaved=True)
-        dt = ops.gemm_nt(dy, st.pT(bkey), alpha=sc)                   # dt = (alpha/r) dy B_down: [M, rp]
-        drop = self.training and self.lora.lora_dropout > 0.0
-        p_, seed = (self.lora.lora_dropout, self._dropout_seed(i, 3)) if drop else (0.0, 0)
-        dgu = ops.linear_lora_swiglu_bwd(dy, st.p(wkey), dt, st.p(akey), gu, p_, seed)
-        xin = act
-        if drop and self.lora_peft_masks and ops.lora_module_masks_ok(act.shape[1], rp):
-            # (down_proj is one peft module: its mask is the same in both modes, so the fused kernel above is exact as it is)
-            ops.lora_wgrad_module_masks(dt, act, p_, [seed], out=st.g(akey))
-        else:
-            if drop:
-                xin = xd if xd is not None else ops.dropout(act, p_, seed)
-            ops.gemm_tn_skinny(dt, xin, out=st.g(akey))
-        ops.gemm_tn_skinny(dy, t, out=st.g(bkey))
+        backward in the epilogue of its input-gradient GEMM (chip-filling shapes: ops.linear_lora_swiglu_ok)."""
+        st = self.store
+        dt = self._lora_dt(dy, i, "down")
+        # (down_proj is one peft module: its mask is the same in both modes, so the fused kernel is exact under per-module masks too)
+        dgu = ops.linear_lora_swiglu_bwd(dy, st.p(f"layers.{i}.wdown"), dt, st.p(f"layers.{i}.lora_down.A"), gu,
+                                         *self._lora_mask(i, "down"))
+        self._lora_wgrads(dy, dt, act, saved, i, "down")
         return dgu
 
     def _layer_fwd(self, i: int, x: torch.Tensor, plan: SplicePlan, cos, sin, save: bool):
@@ -863,11 +864,8 @@ class LlavaDPOModel:
         cfg, st = self.cfg, self.store
         d, H, hd = cfg.hidden, cfg.heads, cfg.head_dim
         S, L = plan.S, plan.L
-        # LoRA under adapter dropout: the kernels that produce a projection's input also write its dropped copy (one pass less over
-        # the activation per projection; the attention output keeps the stand-alone rv_dropout)
-        drop = self._lora_drop() and os.environ.get("RV_LORA_FUSED_DROPOUT", "1") != "0" and not self.lora_peft_masks
-        p_drop = self.lora.lora_dropout if drop else 0.0
-        xnd = xn2d = actd = None
+        drop = self._cur_drop.fused   # this layer's norms and SwiGLU write the dropped copies their consumers' adapters read
+        xnd = xn2d = actd = s_qkv = s_gu = None
         pending = None
         if isinstance(x, tuple):      # RV_RESID_FP32: (fp32 stream, the previous layer's bf16 down-projection branch not yet added to it)
             x, pending = x
@@ -875,7 +873,7 @@ class LlavaDPOModel:
             x, xn, rstd1 = ops.add_rmsnorm_fwd(x, pending, st.p(f"layers.{i}.ln1"), cfg.rms_eps)
             del pending
         elif drop:
-            xn, rstd1, xnd = ops.rmsnorm_fwd_dropout(x, st.p(f"layers.{i}.ln1"), cfg.rms_eps, p_drop, self._dropout_seed(i, 0))
+            xn, rstd1, xnd = ops.rmsnorm_fwd_dropout(x, st.p(f"layers.{i}.ln1"), cfg.rms_eps, *self._lora_mask(i, "qkv"))
         else:
             xn, rstd1 = ops.rmsnorm_fwd(x, st.p(f"layers.{i}.ln1"), cfg.rms_eps)
         rope_cols = (H + cfg.n_kv_heads) * hd
@@ -883,45 +881,40 @@ class LlavaDPOModel:
                 and ops.linear_rope_ok(xn.shape[0], rope_cols + cfg.kv_dim, xn.shape[1], rope_cols, hd)):
             # RoPE in the epilogue of the q|k|v projection, from the fp32 accumulators (round 6): no rope pass, one rounding less on Q / K
             qkv = ops.linear_rope(xn, st.pT(f"layers.{i}.wqkv")[:, :rope_cols + cfg.kv_dim], cos, sin, plan.pos, L, rope_cols, hd)
-            t_qkv = xd_qkv = None
         else:
-            qkv, t_qkv, xd_qkv = self._proj_fwd(xn, i, "qkv", drop_slot=0, xd=xnd)
+            qkv, s_qkv = self._proj_fwd(xn, i, "qkv", xd=xnd)
             ops.rope_inplace(qkv, cos, sin, L, H + cfg.n_kv_heads, hd, pos=plan.pos)      # q heads then k heads
         attn, lse = ops.attn_fwd(qkv, S, L, H, hd, True, 0, d, d + cfg.kv_dim, seg=plan.seg, kv_group=cfg.kv_group, rows=plan.rows)
         if self.resid_fp32:
-            if drop:
-                raise NotImplementedError("RV_RESID_FP32 with the producer-side LoRA dropout kernels (set RV_LORA_FUSED_DROPOUT=0)")
-            o, t_o, xd_o = self._proj_fwd(attn, i, "o", residual=None, drop_slot=1)          # the BRANCH, bf16
+            o, s_o = self._proj_fwd(attn, i, "o", residual=None)          # the BRANCH, bf16
             x_mid, xn2, rstd2 = ops.add_rmsnorm_fwd(x, o, st.p(f"layers.{i}.ln2"), cfg.rms_eps)   # fp32 stream + norm, one pass
             del o
         else:
-            x_mid, t_o, xd_o = self._proj_fwd(attn, i, "o", residual=x, drop_slot=1)
+            x_mid, s_o = self._proj_fwd(attn, i, "o", residual=x)
             if drop:
-                xn2, rstd2, xn2d = ops.rmsnorm_fwd_dropout(x_mid, st.p(f"layers.{i}.ln2"), cfg.rms_eps, p_drop, self._dropout_seed(i, 2))
+                xn2, rstd2, xn2d = ops.rmsnorm_fwd_dropout(x_mid, st.p(f"layers.{i}.ln2"), cfg.rms_eps, *self._lora_mask(i, "gu"))
             else:
                 xn2, rstd2 = ops.rmsnorm_fwd(x_mid, st.p(f"layers.{i}.ln2"), cfg.rms_eps)
         if st.interleave_gu and self.lora is None:   # full fine-tune: SwiGLU in the epilogue of the gate|up GEMM (interleaved weight rows)
             gu, act = ops.linear_swiglu(xn2, st.pT(f"layers.{i}.wgu"))
-            t_gu = xd_gu = None
         elif st.lora_il:              # adapter model, interleaved layout (RV_LORA_FUSE_SWIGLU=1): the same epilogue on the fused-LoRA GEMM
-            gu, act, actd, t_gu, xd_gu = self._lora_gu_fwd(xn2, i, xn2d, p_drop)
+            gu, act, actd, s_gu = self._lora_gu_fwd(xn2, i, xn2d)
         else:
-            gu, t_gu, xd_gu = self._proj_fwd(xn2, i, "gu", drop_slot=2, xd=xn2d)
+            gu, s_gu = self._proj_fwd(xn2, i, "gu", xd=xn2d)
             if drop:
-                act, actd = ops.swiglu_fwd_dropout(gu, p_drop, self._dropout_seed(i, 3))
+                act, actd = ops.swiglu_fwd_dropout(gu, *self._lora_mask(i, "down"))
             else:
                 act = ops.swiglu_fwd(gu)
         if self.resid_fp32:
-            dwn, t_down, xd_down = self._proj_fwd(act, i, "down", residual=None, drop_slot=3, xd=actd)
+            dwn, s_down = self._proj_fwd(act, i, "down", residual=None, xd=actd)
             x_next = (x_mid, dwn)     # the NEXT layer's first norm (or the caller, after the last layer) adds the branch to the stream
         else:
-            x_next, t_down, xd_down = self._proj_fwd(act, i, "down", residual=x_mid, drop_slot=3, xd=actd)
+            x_next, s_down = self._proj_fwd(act, i, "down", residual=x_mid, xd=actd)
         if not save:
             return x_next, None
         keep = self.keep_recomputable
         return x_next, dict(x=x, rstd1=rstd1, qkv=qkv, attn=attn, lse=lse, x_mid=x_mid, rstd2=rstd2, gu=gu,
-                            t_qkv=t_qkv, t_o=t_o, t_gu=t_gu, t_down=t_down,
-                            xd_qkv=xd_qkv, xd_o=xd_o, xd_gu=xd_gu, xd_down=xd_down,
+                            lora_qkv=s_qkv, lora_o=s_o, lora_gu=s_gu, lora_down=s_down,      # ProjSaved per projection (None: no adapters)
                             # 288 GB of HBM: keep the cheap-to-recompute operands too (+1.05 GB / layer at 27 k tokens)
                             # instead of re-running RMSNorm / SwiGLU in backward
                             xn=xn if keep else None, xn2=xn2 if keep else None, act=act if keep else None)
@@ -946,6 +939,7 @@ class LlavaDPOModel:
         if self.training:            # evaluation passes between steps must not shift the dropout seeds of later steps
             self._dropout_step += 1
         self._cur_drop_step = ctx["dropout_step"] = self._dropout_step
+        self._cur_drop = ctx["lora_drop"] = self._resolve_lora_drop()
         if all_rows:
             if save_for_backward:
                 raise ValueError("all_rows is a forward-only mode")
@@ -1019,7 +1013,7 @@ class LlavaDPOModel:
         hook = self.grad_ready_hook
 
         lora = self.lora is not None
-        self._cur_drop_step = ctx.get("dropout_step", 0)
+        self._cur_drop_step, self._cur_drop = ctx.get("dropout_step", 0), ctx.get("lora_drop", LoraDrop())
         scratch_dw = torch.empty(d, dtype=BF16, device=self.device) if lora else None   # gains are frozen under LoRA
 
         def wgrad(dy: torch.Tensor, xin: torch.Tensor, key: str):
@@ -1060,23 +1054,23 @@ class LlavaDPOModel:
                 dgu = ops.linear_swiglu_bwd(dx, st.p(f"layers.{i}.wdown"), c["gu"])
                 ops.gemm_tn(dx, act, out=st.g(f"layers.{i}.wdown"))
                 del act
-            elif st.lora_il:
-                dgu = self._lora_down_bwd_swiglu(dx, act, c["t_down"], i, c["xd_down"], c["gu"])
+            elif st.lora_il and ops.linear_lora_swiglu_ok(dx.shape[0], f, d, self.lora.r_pad):
+                dgu = self._lora_down_bwd_swiglu(dx, act, c["lora_down"], i, c["gu"])
                 del act
             else:
-                dact = self._proj_bwd(dx, act, c["t_down"], i, "down", drop_slot=3, xd=c["xd_down"])
+                dact = self._proj_bwd(dx, act, c["lora_down"], i, "down")
                 del act
-                dgu = ops.swiglu_bwd(dact, c["gu"])
+                dgu = ops.swiglu_bwd(dact, c["gu"], interleaved=st.interleave_gu)
                 del dact
             xn2 = c["xn2"] if c["xn2"] is not None else \
                 ops.rmsnorm_fwd(c["x_mid"], st.p(f"layers.{i}.ln2"), cfg.rms_eps, want_rstd=False)[0]
             c["xn2"] = None
-            dxn2 = self._proj_bwd(dgu, xn2, c["t_gu"], i, "gu", drop_slot=2, xd=c["xd_gu"])
+            dxn2 = self._proj_bwd(dgu, xn2, c["lora_gu"], i, "gu")
             del dgu, xn2
             dx_mid = ops.rmsnorm_bwd(dxn2, c["x_mid"], st.p(f"layers.{i}.ln2"), c["rstd2"], gain_grad(f"layers.{i}.ln2"),
                                      dres=dx)
             del dxn2
-            dattn = self._proj_bwd(dx_mid, c["attn"], c["t_o"], i, "o", drop_slot=1, xd=c["xd_o"])
+            dattn = self._proj_bwd(dx_mid, c["attn"], c["lora_o"], i, "o")
             # dQ / dK leave the attention backward already rotated back (RV_FUSE_ROPE_BWD=0: separate rv_rope_inplace pass)
             dqkv = ops.attn_bwd(c["qkv"], c["attn"], dattn, c["lse"], S, L, H, hd, True, 0, d, d + cfg.kv_dim,
                                 seg=plan.seg, kv_group=cfg.kv_group, rope=(cos, sin, plan.pos) if self.fuse_rope_bwd else None,
@@ -1087,7 +1081,7 @@ class LlavaDPOModel:
             xn = c["xn"] if c["xn"] is not None else \
                 ops.rmsnorm_fwd(c["x"], st.p(f"layers.{i}.ln1"), cfg.rms_eps, want_rstd=False)[0]
             c["xn"] = None
-            dxn = self._proj_bwd(dqkv, xn, c["t_qkv"], i, "qkv", drop_slot=0, xd=c["xd_qkv"])
+            dxn = self._proj_bwd(dqkv, xn, c["lora_qkv"], i, "qkv")
             del dqkv, xn
             dx = ops.rmsnorm_bwd(dxn, c["x"], st.p(f"layers.{i}.ln1"), c["rstd1"], gain_grad(f"layers.{i}.ln1"),
                                  dres=dx_mid)
@@ -1129,6 +1123,7 @@ class LlavaDPOModel:
             x = ops.cast_bf16_to_f32(x)
         plan = SimpleNamespace(S=S, L=L, pos=None, seg=None, rows=None)
         cos, sin = self._rope(L)
+        self._cur_drop = self._resolve_lora_drop()
         for i in range(cfg.layers):
             x, _ = self._layer_fwd(i, x, plan, cos, sin, False)
         if isinstance(x, tuple):

@@ -253,6 +253,20 @@ def gemm_nn_lora_pre(a: torch.Tensor, b: torch.Tensor, a2: torch.Tensor, b2: tor
 _SPLITK_WS = {}
 
 
+def _splitk_plan(R: int, I: int, J: int) -> int:
+    """Number of token-row splits of a skinny [I, J] = [R, I]^T [R, J] product: enough to fill the chip, at least 512 rows each."""
+    return max(1, min(256 // (((I + 255) // 256) * ((J + 255) // 256)), (R + 511) // 512))
+
+
+def _splitk_ws(device, floats: int) -> torch.Tensor:
+    """The fp32 split-K workspace of the current stream of ``device``, grown to at least ``floats`` elements."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _SPLITK_WS.get(key)
+    if ws is None or ws.numel() < floats:
+        ws = _SPLITK_WS[key] = torch.empty(floats, dtype=torch.float32, device=device)
+    return ws
+
+
 def gemm_tn_skinny(p: torch.Tensor, q: torch.Tensor, out: Optional[torch.Tensor] = None, alpha: float = 1.0,
                    splits: int = 0) -> torch.Tensor:
     """gemm_tn for outputs with few 256x256 tiles (LoRA weight gradients): split-K over the token rows so the whole
@@ -265,17 +279,10 @@ def gemm_tn_skinny(p: torch.Tensor, q: torch.Tensor, out: Optional[torch.Tensor]
     if out is None:
         out = torch.empty(I, J, dtype=BF16, device=p.device)
     _chk2d(out, "out")
-    tiles = ((I + 255) // 256) * ((J + 255) // 256)
     if splits <= 0:
-        splits = max(1, min(256 // tiles, (R + 511) // 512))
-    key = (p.device, torch.cuda.current_stream(p.device).cuda_stream)
-    need = splits * I * J
-    ws = _SPLITK_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.float32, device=p.device)
-        _SPLITK_WS[key] = ws
+        splits = _splitk_plan(R, I, J)
     hip.call("rv_gemm_tn_bf16_splitk", p, p.stride(0), q, q.stride(0), out, out.stride(0), R, I, J, float(alpha),
-             int(splits), ws)
+             int(splits), _splitk_ws(p.device, splits * I * J))
     return out
 
 
@@ -351,14 +358,9 @@ def lora_wgrad_module_masks(dt: torch.Tensor, x: torch.Tensor, p: float, seeds, 
     if splits <= 0:
         # gemm_tn_skinny's plan for ONE module's [64, K] gradient: the kernel then sums the token rows in the order of the
         # rv_dropout + rv_gemm_tn_bf16_splitk composition it replaces (same bits), and its (K / 128) x splits workgroups fill the chip
-        splits = max(1, min(256 // ((K + 255) // 256), (R + 511) // 512))
-    key = (x.device, torch.cuda.current_stream(x.device).cuda_stream)
-    need = splits * 64 * G * K
-    ws = _SPLITK_WS.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.float32, device=x.device)
-        _SPLITK_WS[key] = ws
-    hip.call("rv_gemm_tn_lora_masks_bf16", dt, dt.stride(0), x, x.stride(0), out, out.stride(0), R, K, G, float(p), *s, int(splits), ws)
+        splits = _splitk_plan(R, 64, K)
+    hip.call("rv_gemm_tn_lora_masks_bf16", dt, dt.stride(0), x, x.stride(0), out, out.stride(0), R, K, G, float(p), *s, int(splits),
+             _splitk_ws(x.device, splits * 64 * G * K))
     return out
 
 

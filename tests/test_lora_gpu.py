@@ -436,6 +436,36 @@ def test_lora_peft_exact_per_module_dropout_masks(monkeypatch):
     assert (ref_shared["log_prob"].detach() - ref["log_prob"]).abs().max() > 1e-3
 
 
+@pytest.mark.parametrize("ckpt", [False, True])
+@pytest.mark.parametrize("peft_masks", [False, True])
+def test_backward_follows_the_dropout_mode_of_its_forward(monkeypatch, peft_masks, ckpt):
+    """The adapter-dropout mode belongs to the forward: a model switched to eval mode (and to lora_dropout = 0) between a training
+    forward and its backward still differentiates the masked forward - same gradients, bit for bit, as the undisturbed step, with
+    stored activations and with the layer re-run of gradient checkpointing."""
+    _need_gpu()
+    monkeypatch.setenv("SFT_weight", "0.0")
+    monkeypatch.setenv("DPO_weight", "1.0")
+    if peft_masks:
+        monkeypatch.setenv("RV_LORA_PEFT_MASKS", "1")
+    else:
+        monkeypatch.delenv("RV_LORA_PEFT_MASKS", raising=False)
+    cfg = O.tiny_cfg()
+    batch = O.make_synthetic_batch(cfg, 2, 40, 12, seed=43)
+    grads = []
+    for disturb in (False, True):
+        model, _ = _build(cfg, 64, dropout=0.25, share_prefix=False)
+        tr = _trainer(model, gradient_checkpointing=ckpt)
+        assert model.lora_peft_masks == peft_masks and model.gradient_checkpointing == ckpt
+        model.train()
+        tr.compute_loss(model, dict(batch))
+        if disturb:
+            model.eval()
+            model.lora.lora_dropout = 0.0
+        model.backward(model.last_out, model.last_coef)
+        grads.append(model.store.flat_g.clone())
+    assert bool(grads[0].any()) and torch.equal(grads[0], grads[1])
+
+
 @pytest.mark.parametrize("fuse_swiglu", [0, 1])
 def test_lora_full_width_dropout_one_pass_paths_vs_oracle(monkeypatch, fuse_swiglu):
     """(fuse_swiglu = 1: RV_LORA_FUSE_SWIGLU - interleaved gate|up layout, SwiGLU and the dropped activation in the epilogue of the
