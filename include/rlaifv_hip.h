@@ -197,6 +197,13 @@ int rv_lmhead_logp_fwd(const void* h, long ldh, const void* W, long ldw, const i
                        float* pmax, float* psum, float* tgt_logit, int variant, void* stream);
 int rv_logp_finish(const float* pmax, const float* psum, const float* tgt_logit, int nblk, int M, float* lse,
                    float* logp, void* stream);
+/* finish + unpack (the packed log-prob precompute): the lse / logp of rv_logp_finish (same device code, bit-equal), then row
+ * m's logp is written to per_token[dst_a[m]], per_token[dst_b[m]] and compact[dst_c[m]]; a negative index is skipped, one
+ * out of range too.  Every destination must have one writer (plain stores, no atomics); slots no row names keep the
+ * caller's fill. */
+int rv_logp_finish_unpack(const float* pmax, const float* psum, const float* tgt_logit, int nblk, int M, const int* dst_a,
+                          const int* dst_b, const int* dst_c, float* per_token, long n_per_token, float* compact, int n_compact,
+                          void* stream);
 int rv_lmhead_logp_bwd(const void* h, long ldh, const void* W, long ldw, const int* tgt, const float* lse,
                        const float* coef, void* dlogits, long ldd, int M, int V, int V_valid, int K, int variant,
                        void* stream);

@@ -887,22 +887,48 @@ __global__ void adamw_kernel(bf16_t* __restrict__ p, float* __restrict__ master,
 
 // ------------------------------------------------------------------ log-prob reductions + DPO loss
 // lse[m] = log sum_n exp(logit[m][n]) from per-64-column partials; logp[m] = tgt_logit[m] - lse[m]
-__global__ void logp_finish_kernel(const float* __restrict__ pmax, const float* __restrict__ psum,
-                                   const float* __restrict__ tgt_logit, int nblk, int M,
-                                   float* __restrict__ lse, float* __restrict__ logp) {
-  const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (m >= M) return;
-  const int lane = threadIdx.x & 63;
+// One wave per row; every lane returns the row's lse.  Shared by both finish kernels: same operations in the same order.
+__device__ __forceinline__ float logp_row_lse(const float* __restrict__ pmax, const float* __restrict__ psum, int nblk, int m,
+                                              int lane) {
   float mx = -INFINITY;
   for (int i = lane; i < nblk; i += 64) mx = fmaxf(mx, pmax[(long)m * nblk + i]);
   mx = wave_max(mx);
   float s = 0.f;
   for (int i = lane; i < nblk; i += 64) s += psum[(long)m * nblk + i] * __expf(pmax[(long)m * nblk + i] - mx);
   s = wave_sum(s);
+  return mx + logf(s);
+}
+
+__global__ void logp_finish_kernel(const float* __restrict__ pmax, const float* __restrict__ psum,
+                                   const float* __restrict__ tgt_logit, int nblk, int M,
+                                   float* __restrict__ lse, float* __restrict__ logp) {
+  const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (m >= M) return;
+  const int lane = threadIdx.x & 63;
+  const float l = logp_row_lse(pmax, psum, nblk, m, lane);
   if (lane == 0) {
-    const float l = mx + logf(s);
     lse[m] = l;
     logp[m] = tgt_logit[m] - l;
+  }
+}
+
+// finish + unpack (the packed log-prob precompute): row m's logp goes to its one or two slots of the per-token matrix and to
+// its slot of the compact vector of selected rows; a negative index means no such slot.  Every destination has one writer.
+__global__ void logp_finish_unpack_kernel(const float* __restrict__ pmax, const float* __restrict__ psum,
+                                          const float* __restrict__ tgt_logit, int nblk, int M,
+                                          const int* __restrict__ dst_a, const int* __restrict__ dst_b,
+                                          const int* __restrict__ dst_c, float* __restrict__ per_token, long n_per_token,
+                                          float* __restrict__ compact, int n_compact) {
+  const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (m >= M) return;
+  const int lane = threadIdx.x & 63;
+  const float l = logp_row_lse(pmax, psum, nblk, m, lane);
+  if (lane == 0) {
+    const float lp = tgt_logit[m] - l;
+    const int a = dst_a[m], b = dst_b[m], c = dst_c[m];
+    if (a >= 0 && a < n_per_token) per_token[a] = lp;
+    if (b >= 0 && b < n_per_token) per_token[b] = lp;
+    if (c >= 0 && c < n_compact) compact[c] = lp;
   }
 }
 
@@ -1424,6 +1450,19 @@ int rv_logp_finish(const float* pmax, const float* psum, const float* tgt_logit,
   if (M == 0) return 0;
   hipLaunchKernelGGL(logp_finish_kernel, dim3((M + 3) / 4), dim3(256), 0, STREAM(stream), pmax, psum, tgt_logit, nblk,
                      M, lse, logp);
+  RV_CHECK_LAUNCH();
+  return 0;
+}
+
+int rv_logp_finish_unpack(const float* pmax, const float* psum, const float* tgt_logit, int nblk, int M, const int* dst_a,
+                          const int* dst_b, const int* dst_c, float* per_token, long n_per_token, float* compact, int n_compact,
+                          void* stream) {
+  if (M == 0) return 0;
+  RV_REQUIRE(nblk > 0 && M > 0 && n_per_token >= 0 && n_compact >= 0, "rv_logp_finish_unpack: nblk, M > 0; sizes >= 0");
+  RV_REQUIRE(dst_a && dst_b && dst_c, "rv_logp_finish_unpack: the three destination tables are required (-1 = no slot)");
+  RV_REQUIRE((per_token || n_per_token == 0) && (compact || n_compact == 0), "rv_logp_finish_unpack: NULL output with a non-zero size");
+  hipLaunchKernelGGL(logp_finish_unpack_kernel, dim3((M + 3) / 4), dim3(256), 0, STREAM(stream), pmax, psum, tgt_logit, nblk,
+                     M, dst_a, dst_b, dst_c, per_token, n_per_token, compact, n_compact);
   RV_CHECK_LAUNCH();
   return 0;
 }

@@ -139,7 +139,7 @@ class RLAIFVDataset(torch.utils.data.Dataset):
     """Rows of the ``*logp*.parquet`` files under ``data_dir`` (written by inference_logp.write_logp_to_preference_parquet)."""
 
     def __init__(self, data_dir: str, reference_model=None, tokenizer=None, image_token_len=None, img_processor=None,
-                 use_im_start_end: bool = False, is_llava15: bool = True):
+                 use_im_start_end: bool = False, is_llava15: bool = True, precompute_packed: Optional[bool] = None):
         import pandas as pd
         os.makedirs(data_dir, exist_ok=True)
 
@@ -160,7 +160,7 @@ class RLAIFVDataset(torch.utils.data.Dataset):
             rows = pd.concat([pd.read_parquet(f) for f in raw], ignore_index=True).to_dict("records")
             inference_logp(reference_model, tokenizer,
                            PreferenceInferenceDataset(rows, tokenizer, image_token_len, img_processor, use_im_start_end),
-                           data_dir, is_llava15=is_llava15)
+                           data_dir, is_llava15=is_llava15, packed=precompute_packed)
         files = logp_files()
         self.data = pd.concat([pd.read_parquet(os.path.join(data_dir, f)) for f in files], ignore_index=True).to_dict("records")
 
@@ -191,7 +191,7 @@ class DPODataset(torch.utils.data.Dataset):
         self.tokenizer = tokenizer
         self.list_data_dict = RLAIFVDataset(data_dir, reference_model, tokenizer, multimodal_cfg.get("image_token_len"),
                                             multimodal_cfg.get("image_processor"), multimodal_cfg.get("use_im_start_end", False),
-                                            is_llava15=True)
+                                            is_llava15=True, precompute_packed=multimodal_cfg.get("precompute_packed"))
         self.multimodal_cfg = dict(multimodal_cfg, keep_image_tag=True)
 
     def __len__(self):

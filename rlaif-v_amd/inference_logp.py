@@ -16,7 +16,7 @@ import itertools
 import json
 import os
 from functools import partial
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import torch
 
@@ -74,12 +74,24 @@ class PreferenceInferenceDataset(torch.utils.data.Dataset):
         return len(self.data)
 
 
-def get_multimodal_sample_logps(model, dataloader, tokenizer=None, is_llava15: bool = True):
+def precompute_packed_default() -> bool:
+    """RV_PRECOMPUTE_PACKED (default "0"): run the precompute on the packed training layout (get_multimodal_sample_logps)."""
+    return os.environ.get("RV_PRECOMPUTE_PACKED", "0") != "0"
+
+
+def get_multimodal_sample_logps(model, dataloader, tokenizer=None, is_llava15: bool = True, packed: bool = False):
     """Returns (win_logp, win_avg_logp, win_per_token_logp, rej_logp, rej_avg_logp, rej_per_token_logp) as Python
     lists, one entry per sample; per-token lists have spliced_length - 1 entries like the reference's.
     ``is_llava15=False`` is the generic branch (:253-261, ``model(input_ids, labels, images)``) for a model whose splice keeps
     the text positions (OmniLMM): the same all-rows forward, and the per-token lists then have T - 1 entries, aligned with
-    the collator's token weights."""
+    the collator's token weights.
+    ``packed``: one forward per batch on the packed training layout ``[shared prefix | chosen | rejected]`` (the model's
+    ``share_prefix`` / ``pad_free`` setting) instead of one un-packed forward per branch: the images are encoded once, the shared
+    prefix is evaluated once, and the stored values are what the packed training forward computes on the same weights, bit for
+    bit (same plan, same launches; sums by rv_seq_sum over the selected rows).  Per-token lists are cut to each row's own
+    spliced length - 1, like the reference at its batch size 1 (``is_llava15=False``: they keep the T - 1 text columns)."""
+    if packed:
+        return _packed_sample_logps(model, dataloader, is_llava15)
     if not is_llava15 and not getattr(model, "splice_keeps_positions", False):
         raise ValueError("is_llava15=False (the generic precompute branch) needs a model whose image splice keeps the text "
                          "positions (OmniLMM)")
@@ -103,6 +115,33 @@ def get_multimodal_sample_logps(model, dataloader, tokenizer=None, is_llava15: b
         avg = torch.cat(parts[key][1]).tolist() if parts[key][1] else []
         per = [row for t in parts[key][2] for row in t.cpu().tolist()]
         out[key] = (logp, avg, per)
+    w, r = out["win"], out["rej"]
+    return w[0], w[1], w[2], r[0], r[1], r[2]
+
+
+def _packed_sample_logps(model, dataloader, is_llava15: bool):
+    if not getattr(model, "share_prefix", False):
+        raise ValueError("the packed precompute runs the packed training layout: the model must have share_prefix set")
+    if not is_llava15 and not getattr(model, "splice_keeps_positions", False):
+        raise ValueError("is_llava15=False (the generic precompute branch) needs a model whose image splice keeps the text "
+                         "positions (OmniLMM)")
+    sums, avgs, per, lens = [], [], [], []          # device tensors until the loop is over (no host round trip per batch)
+    model.eval()
+    for batch in dataloader:
+        res = model.forward_logps(batch["concatenated_input_ids"], batch["concatenated_labels"], batch["images"],
+                                  save_for_backward=False, all_rows=True, packed=True)
+        sums.append(res.seq_logp.float().clone())
+        avgs.append((res.seq_logp / res.seq_cnt).float())
+        per.append(res.per_token_logp)
+        lens.append(res.plan.ev_len if is_llava15 else [res.per_token_logp.shape[1]] * res.plan.n_seq)
+    out = {"win": ([], [], []), "rej": ([], [], [])}
+    for s_t, a_t, p_t, ln in zip(sums, avgs, per, lens):
+        B = s_t.numel() // 2
+        s_l, a_l, p_l = s_t.tolist(), a_t.tolist(), p_t.cpu().tolist()
+        for key, r0 in (("win", 0), ("rej", B)):
+            out[key][0].extend(s_l[r0:r0 + B])
+            out[key][1].extend(a_l[r0:r0 + B])
+            out[key][2].extend(p_l[r][:ln[r]] for r in range(r0, r0 + B))
     w, r = out["win"], out["rej"]
     return w[0], w[1], w[2], r[0], r[1], r[2]
 
@@ -132,13 +171,16 @@ def write_logp_to_preference_parquet(origin_data, cache_file: str, logps: Sequen
 
 
 def inference_logp(model, tokenizer, dataset, cache_file: str, batch_size: int = 1, num_workers: int = 0,
-                   is_llava15: bool = True):
-    """``dataset`` plays the role of the reference's PreferenceInferenceDataset: ``dataset[i]`` -> (rej_dict, win_dict)
+                   is_llava15: bool = True, packed: Optional[bool] = None):
+    """``packed``: run the precompute on the packed training layout (get_multimodal_sample_logps); None reads RV_PRECOMPUTE_PACKED.
+    ``dataset`` plays the role of the reference's PreferenceInferenceDataset: ``dataset[i]`` -> (rej_dict, win_dict)
     and ``dataset.data[i]`` -> the original row (question / chosen / rejected / image ...)."""
     pad_id = getattr(tokenizer, "pad_token_id", 0) if tokenizer is not None else 0
     loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, collate_fn=partial(preference_collator_fn, pad_token_id=pad_id),
                                          num_workers=num_workers, shuffle=False, sampler=InferenceSampler(len(dataset)))
-    outputs = get_multimodal_sample_logps(model, loader, tokenizer, is_llava15=is_llava15)
+    if packed is None:
+        packed = precompute_packed_default()
+    outputs = get_multimodal_sample_logps(model, loader, tokenizer, is_llava15=is_llava15, packed=packed)
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         world = torch.distributed.get_world_size()
         merged = []

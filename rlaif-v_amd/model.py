@@ -922,7 +922,7 @@ class LlavaDPOModel:
     # ------------------------------------------------------------------ forward
     def forward_logps(self, input_ids: torch.Tensor, labels: torch.Tensor, images: torch.Tensor,
                       save_for_backward: bool = True, all_rows: bool = False, label_shift: int = 1,
-                      token_weight: Optional[torch.Tensor] = None) -> StepOutput:
+                      token_weight: Optional[torch.Tensor] = None, packed: bool = False) -> StepOutput:
         """Everything of get_beta_and_logps up to ``get_batch_logps``: returns per-sequence log-prob sums
         and counts (muffin/eval/muffin_inference_logp.py:82-115) without materialising logits.
         ``all_rows`` (forward only, reference layout): evaluate EVERY position like
@@ -930,7 +930,22 @@ class LlavaDPOModel:
         the reference stores in its ``logps`` parquet column.
         ``token_weight`` [2B, T-1] (token-weighted DPO, position-keeping splices only): the plan gathers it onto the selected
         rows, ``seq_logp`` / ``seq_cnt`` become the weighted sum and the weighted count (compute_weighted_logp,
-        trainers.py:128-137) and backward scales each row's coefficient by its weight."""
+        trainers.py:128-137) and backward scales each row's coefficient by its weight.
+        ``packed`` (with ``all_rows``; input_ids / labels [2B, T] wins then rejects, B images): the all-positions evaluation on
+        the packed TRAINING layout - the same plan, layer stack and launches as the training forward, so the values are the
+        training step's bit for bit.  ``per_token_logp`` is the [2B, ld] matrix (row s owns its first ``plan.ev_len[s]``
+        entries, the rest keep the fill 0), ``seq_logp`` / ``seq_cnt`` are rv_seq_sum over the compact vector of selected rows."""
+        if packed:
+            if not all_rows:
+                raise ValueError("packed=True is the all-positions precompute on the packed layout: pass all_rows=True")
+            if save_for_backward:
+                raise ValueError("all_rows is a forward-only mode")
+            if label_shift != 1:
+                raise ValueError("packed=True needs the label_shift=1 convention (the packed layout has no MiniCPM variant)")
+            if token_weight is not None:
+                raise ValueError("all_rows returns per-token log-probs; token weights apply to the selected-row step")
+            if input_ids.shape[0] != 2 * len(images):
+                raise ValueError("packed=True takes [2B, T] wins-then-rejects rows and B images")
         cfg, st = self.cfg, self.store
         d, H, hd, f = cfg.hidden, cfg.heads, cfg.head_dim, cfg.ffn
         B = len(images)                  # tensor [B, 3, H, W] or a list of raw uint8 [H, W, 3] images
@@ -940,7 +955,10 @@ class LlavaDPOModel:
             self._dropout_step += 1
         self._cur_drop_step = ctx["dropout_step"] = self._dropout_step
         self._cur_drop = ctx["lora_drop"] = self._resolve_lora_drop()
-        if all_rows:
+        if packed:
+            plan = build_packed_plan(input_ids, labels, cfg.n_image_tokens, B, cfg.model_max_length, cfg.pad_token_id,
+                                     splicer=self._row_splicer(), pad_free=self.pad_free, all_rows=True)
+        elif all_rows:
             if save_for_backward:
                 raise ValueError("all_rows is a forward-only mode")
             if token_weight is not None:
@@ -984,6 +1002,8 @@ class LlavaDPOModel:
             x = x_next
         if isinstance(x, tuple):
             x = ops.add_f32_bf16(*x)          # the last layer's branch joins the fp32 stream
+        if packed:
+            return self._packed_all_rows_logps(x, plan)
         n_sel = plan.n_sel
         n_pad = max(64, ops.round_up(n_sel, 64))
         hsel = torch.zeros(n_pad, d, dtype=BF16, device=self.device)
@@ -1001,6 +1021,28 @@ class LlavaDPOModel:
             ctx.update(layers=layers_ctx, x_final=x, hsel=hsel, rstd_f=rstd_f, lse_v=lse_v, w_rows=w_rows, N=N, B=B)
             out.ctx = ctx
         return out
+
+    def _packed_all_rows_logps(self, x: torch.Tensor, plan: SplicePlan) -> StepOutput:
+        """Final norm + LM head on every evaluated row of the packed layout (plan.ev_*), then rv_logp_finish_unpack: one launch
+        writes each log-prob to its per-token slot(s) and, for the rows the training step selects, to the compact vector that
+        rv_seq_sum reduces with the plan's own seq_off - the training step's sums.  A row's LM-head result does not depend on
+        the other rows of the launch as long as the GEMM kernel is the same, and the library picks that kernel by row count:
+        the launch here is given the kernel the training step's n_sel rows would get."""
+        cfg, st = self.cfg, self.store
+        n_ev, n_sel, ld = plan.n_ev, plan.n_sel, plan.ev_ld
+        per_token = torch.zeros(plan.n_seq, ld, dtype=torch.float32, device=self.device)
+        compact = torch.zeros(n_sel, dtype=torch.float32, device=self.device)
+        if n_ev > 0:
+            hev = torch.zeros(max(64, ops.round_up(n_ev, 64)), cfg.hidden, dtype=BF16, device=self.device)
+            ops.rmsnorm_fwd(x, st.p("model.norm.weight"), cfg.rms_eps, row_idx=plan.ev_idx, out=hev[:n_ev], want_rstd=False)
+            W = st.p("lm_head.weight")
+            v_train = ops.gemm_auto_variant(n_sel, W.shape[0]) if n_sel > 0 else -1
+            variant = -1 if v_train == ops.gemm_auto_variant(n_ev, W.shape[0]) else v_train
+            ops.lmhead_logp_unpack(hev, W, plan.ev_tgt, n_ev, plan.ev_dst_a, plan.ev_dst_b, plan.ev_dst_c, per_token, compact,
+                                   v_valid=cfg.vocab, variant=variant)
+        seq_logp, seq_cnt = ops.seq_sum(compact, plan.seq_off, plan.n_seq)
+        return StepOutput(loss=None, scalars=None, per_pair=None, seq_logp=seq_logp, seq_cnt=seq_cnt,
+                          per_token_logp=per_token, plan=plan)
 
     # ------------------------------------------------------------------ backward
     def backward(self, out: StepOutput, coef: torch.Tensor):

@@ -702,6 +702,37 @@ def lmhead_logp_fwd(h: torch.Tensor, w: torch.Tensor, tgt: torch.Tensor, n_rows:
     return logp, lse
 
 
+def gemm_auto_variant(M: int, N: int) -> int:
+    """The NT GEMM kernel the library picks for an [M, N] output when no variant is forced (gemm.hip dispatch: the 256 x 256
+    tile kernel from 192 tiles on)."""
+    return 3 if ((M + 255) // 256) * ((N + 255) // 256) >= 192 else 1
+
+
+def lmhead_logp_unpack(h: torch.Tensor, w: torch.Tensor, tgt: torch.Tensor, n_rows: int, dst_a: torch.Tensor,
+                       dst_b: torch.Tensor, dst_c: torch.Tensor, per_token: torch.Tensor, compact: torch.Tensor,
+                       v_valid: Optional[int] = None, variant: int = -1):
+    """lmhead_logp_fwd whose finish scatters every row's log-prob (rv_logp_finish_unpack): to per_token.flatten()[dst_a],
+    [dst_b] and compact[dst_c], negative indices skipped.  per_token / compact are the caller's (pre-filled) fp32 buffers.
+    ``variant``: the LM-head GEMM kernel (-1: the library's choice for n_rows)."""
+    _chk2d(h, "h"), _chk2d(w, "w")
+    V = w.shape[0]
+    v_valid = V if v_valid is None else v_valid
+    nblk = V // 64
+    for name, t in (("dst_a", dst_a), ("dst_b", dst_b), ("dst_c", dst_c), ("tgt", tgt)):
+        if t.dtype != torch.int32 or t.numel() < n_rows or not t.is_contiguous():
+            raise ValueError(f"lmhead_logp_unpack: {name} must be contiguous int32 with at least {n_rows} entries")
+    for name, t in (("per_token", per_token), ("compact", compact)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"lmhead_logp_unpack: {name} must be contiguous fp32")
+    dev = h.device
+    pmax = torch.empty(n_rows, nblk, dtype=torch.float32, device=dev)
+    psum = torch.empty(n_rows, nblk, dtype=torch.float32, device=dev)
+    tl = torch.zeros(n_rows, dtype=torch.float32, device=dev)
+    hip.call("rv_lmhead_logp_fwd", h, h.stride(0), w, w.stride(0), tgt, n_rows, V, v_valid, h.shape[1], pmax, psum, tl, int(variant))
+    hip.call("rv_logp_finish_unpack", pmax, psum, tl, nblk, n_rows, dst_a, dst_b, dst_c, per_token, per_token.numel(),
+             compact, compact.numel())
+
+
 def lmhead_logp_bwd(h, w, tgt, lse, coef, n_rows: int, out: Optional[torch.Tensor] = None, v_valid: Optional[int] = None):
     """dlogits bf16 [rows_padded, V]; rows >= n_rows and columns >= v_valid are zero."""
     V = w.shape[0]

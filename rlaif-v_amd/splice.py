@@ -55,6 +55,16 @@ class SplicePlan:
     row_len: Optional[torch.Tensor] = None    # int32 [S] ... and its length; L is then the LONGEST row (grid / lse stride / RoPE table)
     n_tokens: int = 0                         # rows of the token-major activation buffers (S * L when rectangular)
     w_sel: Optional[torch.Tensor] = None      # fp32 [n_sel] token weight of each selected row (token-weighted DPO), else None
+    # all-positions evaluation of the packed layout (build_packed_plan(all_rows=True), the packed log-prob precompute): every
+    # packed row with a successor in its own sequence, pair by pair in buffer order [prefix | chosen | rejected]
+    ev_idx: Optional[torch.Tensor] = None     # int32 [n_ev] flat row n that is evaluated
+    ev_tgt: Optional[torch.Tensor] = None     # int32 [n_ev] its next label, token id 0 where that label is -100 (return_all=True)
+    ev_dst_a: Optional[torch.Tensor] = None   # int32 [n_ev] slot s * ev_ld + t of the per-token matrix [n_seq, ev_ld]
+    ev_dst_b: Optional[torch.Tensor] = None   # int32 [n_ev] second slot (prefix rows: the rejected sequence's copy), else -1
+    ev_dst_c: Optional[torch.Tensor] = None   # int32 [n_ev] slot in the compact vector = its index in sel_idx / tgt, else -1
+    ev_len: Optional[List[int]] = None        # per sequence n_s - 1: the per-token entries it owns (n_s: spliced, truncated, pads dropped)
+    ev_ld: int = 0                            # columns of the per-token matrix
+    n_ev: int = 0
 
     def to(self, device) -> "SplicePlan":
         kw = {}
@@ -238,9 +248,29 @@ def build_splice_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_token
                       n_real_tokens=int(sum(x.numel() for x in rows_src)), n_tokens=S * L, w_sel=w_sel)
 
 
+def _eval_rows(cl: torch.Tensor, rl: torch.Tensor, sh: int):
+    """The evaluated rows of one pair (build_packed_plan(all_rows=True)) from its chosen / rejected labels and shared length:
+    (row offset in the packed row, position t, branch 0 | 1, target, rank among its sequence's real targets or -1)."""
+    Lc, Lr = cl.numel(), rl.numel()
+    assert sh <= min(Lc, Lr) - 1
+    # prefix rows are evaluated once for both sequences: both must ask for the masked-position target there
+    assert bool((cl[1:sh + 1] == IGNORE_INDEX).all()) and bool((rl[1:sh + 1] == IGNORE_INDEX).all()), \
+        "a shared-prefix row predicts a real target"
+    tc, tr = torch.arange(0, Lc - 1), torch.arange(sh, Lr - 1)
+    t = torch.cat([tc, tr])
+    row = torch.cat([tc, Lc + (tr - sh)])
+    br = torch.cat([torch.zeros_like(tc), torch.ones_like(tr)])
+    nxt = torch.cat([cl[1:], rl[sh + 1:]])
+    real = nxt != IGNORE_INDEX
+    rank_c = torch.cumsum(real[:Lc - 1].long(), 0) - 1
+    rank_r = torch.cumsum(real[Lc - 1:].long(), 0) - 1
+    rank = torch.where(real, torch.cat([rank_c, rank_r]), torch.full_like(t, -1))
+    return row, t, br, torch.where(real, nxt, torch.zeros_like(nxt)), rank
+
+
 def build_packed_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_tokens: int, n_images: int,
                       max_len: Optional[int], pad_token_id: int = 0, splicer=None, pad_free: bool = False,
-                      token_weight: Optional[torch.Tensor] = None) -> SplicePlan:
+                      token_weight: Optional[torch.Tensor] = None, all_rows: bool = False) -> SplicePlan:
     """One row per pair: [shared prefix | chosen branch | rejected branch] (module docstring).
     input_ids / labels: [2B, T], wins then rejects.
     ``pad_free``: the B packed rows are CONCATENATED (row b starts at row_off[b], no inter-row padding) instead of being
@@ -250,10 +280,17 @@ def build_packed_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_token
     attention kernels take (row_off, row_len) and the RoPE position table is indexed by buffer row.  Identical index tables up
     to the row renumbering: selected rows / targets / sequence offsets keep their (sequence, position) order.
     ``token_weight`` [2B, T-1]: chosen rows take token_weight[b, i], rejected rows token_weight[B+b, i] for the text position
-    i of the row (``w_sel``, same order as ``tgt``)."""
+    i of the row (``w_sel``, same order as ``tgt``).
+    ``all_rows``: the same plan plus the ``ev_*`` tables of the all-positions evaluation (get_batch_logps(return_all=True),
+    muffin_inference_logp.py:93-115, on the packed row): position t of sequence s, t < n_s - 1, is packed row t of its pair when
+    it is chosen or lies in the shared prefix, row Lc + (t - sh) when it is rejected; its target is label[s][t + 1] or token
+    id 0.  A prefix row is evaluated ONCE and lands in both sequences' per-token rows (sh <= first target - 1: both want
+    target 0 there); the rows with a real target also land in the compact vector, at their index in ``sel_idx``."""
     input_ids = input_ids.cpu().long()
     labels = labels.cpu().long()
     S2 = input_ids.shape[0]
+    if all_rows and token_weight is not None:
+        raise ValueError("all_rows returns per-token log-probs; token weights apply to the selected-row step")
     token_weight = _check_token_weight(token_weight, splicer, S2)
     if S2 % 2:
         raise ValueError("packed layout needs wins followed by the same number of rejects")
@@ -272,6 +309,7 @@ def build_packed_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_token
     sel_rows: List[List[torch.Tensor]] = [[None] * B, [None] * B]          # [branch][pair] -> row offsets in the packed row
     sel_tgts: List[List[torch.Tensor]] = [[None] * B, [None] * B]
     sel_w: List[List[torch.Tensor]] = [[None] * B, [None] * B]
+    ev: List[Tuple[torch.Tensor, ...]] = []                                # per pair (all_rows)
     for b in range(B):
         cs, cl, rs, rl = rows_src[b], rows_lab[b], rows_src[B + b], rows_lab[B + b]
         n = min(cs.numel(), rs.numel())
@@ -291,6 +329,8 @@ def build_packed_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_token
         sel_rows[1][b], sel_tgts[1][b] = Lc + (ri - sh), rl[1:][ri]
         if token_weight is not None:
             sel_w[0][b], sel_w[1][b] = _gather_weight(token_weight, b, ci), _gather_weight(token_weight, B + b, ri)
+        if all_rows:
+            ev.append(_eval_rows(cl, rl, sh))
     L = max(int(x.numel()) for x in packed_src)
     lens = [int(x.numel()) for x in packed_src]
     if pad_free:
@@ -325,7 +365,25 @@ def build_packed_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_token
     seq_off = torch.zeros(S2 + 1, dtype=torch.int32)
     seq_off[1:] = torch.cumsum(torch.tensor(counts), 0).to(torch.int32)
     uniq, seg_off, pos_sorted, a, bb = _tables(flat, max(n_images, 1) * n_img_tokens)
-    return SplicePlan(S=B, L=L, n_seq=S2, src=flat.to(torch.int32), labels=None, sel_idx=sel, tgt=tgt, seq_off=seq_off,
+    evkw = {}
+    if all_rows:
+        ev_len = [int(x.numel()) - 1 for x in rows_src]
+        ld = max(ev_len)
+        if getattr(splicer, "keeps_positions", False):
+            # row position = text position: the per-token rows keep the collator's T - 1 columns (its token weights' layout)
+            ld = max(ld, min(input_ids.shape[1], max_len or input_ids.shape[1]) - 1)
+        rows, tg, da, db, dc = [], [], [], [], []
+        for b, (row, t, br, tgt_b, rank) in enumerate(ev):
+            s = b + br * B                                                 # the sequence that owns the row (prefix: chosen)
+            rows.append(starts[b] + row)
+            tg.append(tgt_b)
+            da.append(s * ld + t)
+            db.append(torch.where(t < shs[b], (B + b) * ld + t, torch.full_like(t, -1)))
+            dc.append(torch.where(rank >= 0, seq_off[s.long()].long() + rank, torch.full_like(rank, -1)))
+        i32 = lambda xs: torch.cat(xs).to(torch.int32)                     # noqa: E731
+        evkw = dict(ev_idx=i32(rows), ev_tgt=i32(tg), ev_dst_a=i32(da), ev_dst_b=i32(db), ev_dst_c=i32(dc), ev_len=ev_len,
+                    ev_ld=ld, n_ev=int(sum(x.numel() for x in rows)))
+    return SplicePlan(**evkw, S=B, L=L, n_seq=S2, src=flat.to(torch.int32), labels=None, sel_idx=sel, tgt=tgt, seq_off=seq_off,
                       seq_of_row=seq_of, uniq_ids=uniq, seg_off=seg_off, pos_sorted=pos_sorted, feat_src_a=a,
                       feat_src_b=bb, n_sel=int(sel.numel()), pos=pos_flat.to(torch.int32),
                       seg_sh=torch.tensor(shs, dtype=torch.int32), seg_e1=torch.tensor(e1s, dtype=torch.int32),

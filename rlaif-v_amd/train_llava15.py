@@ -61,6 +61,7 @@ class DataArguments:
     dpo_beta: float = 0.5
     dpo_token_weight: float = 3.0
     shuffle_data: bool = True
+    precompute_packed: bool = False        # reference log-prob precompute on the packed training layout (else: RV_PRECOMPUTE_PACKED)
 
 
 @dataclass
@@ -123,7 +124,8 @@ def make_dpo_data_module(tokenizer, data_args: DataArguments, reference_model=No
                   use_im_start_end=getattr(data_args, "mm_use_im_start_end", False),
                   image_processor=getattr(data_args, "image_processor", None),
                   data_source_names=data_args.data_source_names, data_source_weights=data_args.data_source_weights,
-                  shuffle_data=data_args.shuffle_data)
+                  shuffle_data=data_args.shuffle_data,
+                  precompute_packed=True if getattr(data_args, "precompute_packed", False) else None)
     train_dataset = DPODataset(tokenizer=tokenizer, data_dir=data_args.data_dir, multimodal_cfg=mm_cfg,
                                reference_model=reference_model)
     if int(os.environ.get("RANK", "0")) == 0:
