@@ -207,6 +207,16 @@ int rv_logp_finish_unpack(const float* pmax, const float* psum, const float* tgt
 int rv_lmhead_logp_bwd(const void* h, long ldh, const void* W, long ldw, const int* tgt, const float* lse,
                        const float* coef, void* dlogits, long ldd, int M, int V, int V_valid, int K, int variant,
                        void* stream);
+/* Next-token scores of the yes / no feedback stage (muffin/llava15_gen_data.py:266-333, omnilmm/omnilmm_gen_data.py:245-300:
+ * generate(max_new_tokens=1, output_scores=True), softmax of scores[0] read at a few ids).  logits: fp32 [M][ldl], READ ONLY;
+ * the softmax runs over the columns [0, V_valid) - the columns behind them are vocabulary padding.  Repetition penalty (HF
+ * RepetitionPenaltyLogitsProcessor; penalty == 1 or seen_off == NULL: off): seen_ids[seen_off[m] .. seen_off[m+1]) are the
+ * token ids of row m's prompt, a logit l at such an id becomes l / penalty if l > 0, else l * penalty.
+ *   probs / logp [M][K]: softmax / log-softmax at want_ids[k] (an id outside [0, V_valid): 0 / -inf);  lse [M];
+ *   argmax [M]: greedy next token, the LOWEST index among equal maxima.  One workgroup per row, fixed reduction order. */
+int rv_next_token_scores(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids,
+                         float penalty, const int* want_ids, int K, float* probs, float* logp, int* argmax, float* lse,
+                         void* stream);
 /* (per_token_logps * loss_mask).sum(-1) and loss_mask.sum(-1) of get_batch_logps (:103-104); rows of
  * sequence s are seq_off[s] .. seq_off[s+1]; optional per-row weight (compute_weighted_logp,
  * muffin/train/trainers.py:128-137). Fixed summation order. */
@@ -237,6 +247,18 @@ int rv_row_coef(const float* coef, const int* seq_of_row, const float* weight, f
 int rv_attn_fwd(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, void* out, long ldo, float* lse, int S,
                 int L, int H, int hd, int causal, float scale, const int* seg_sh, const int* seg_e1, int kv_group,
                 const int* row_off, const int* row_len, void* stream);
+/* N-branch packed rows (the yes / no feedback stage: many short questions about one image).  Row s holds
+ *   [shared prefix | branch 0 | branch 1 | ... | branch N-1]; seg_sh[s] is the prefix length and q_lo (int32, one entry per TOKEN
+ *   row of the buffer, indexed like rv_attn_bwd's rope_pos: row_off[s] + i under pad-free rows, s * L + i otherwise) gives, for
+ *   query i, the first key - relative to the row's first token - of its own branch.  Always causal:
+ *       query i attends key j  <=>  j <= i  &&  (j < seg_sh[s]  ||  j >= q_lo[i]).
+ *   q_lo[i] is ignored for i < seg_sh[s]; for the other queries seg_sh[s] <= q_lo[i] <= i, and q_lo does not decrease inside a
+ *   row.  The CALLER guarantees these conditions (rlaif-v_amd/splice.py check_branch_rows); the kernel does not check them.
+ *   Everything else (lse, out, kv_group, row_off / row_len, hd in {64, 128}) as in rv_attn_fwd, whose main loop this is: with two
+ *   branches it gives rv_attn_fwd(seg_sh, seg_e1)'s bits, with one branch plain causal rv_attn_fwd's.  Forward only. */
+int rv_attn_fwd_branches(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, void* out, long ldo, float* lse,
+                         int S, int L, int H, int hd, float scale, const int* seg_sh, const int* q_lo, int kv_group,
+                         const int* row_off, const int* row_len, void* stream);
 /* kv_group (both calls): grouped-query attention as in HF Mistral / Llama-3 (`repeat_kv`): H query heads share
  * H / kv_group key/value heads, query head h reads kv head h / kv_group (K at k_col0 + (h / kv_group) * hd); 1 = MHA.
  * backward (hd = 128): O = the forward output (rv_attn_fwd's `out`), delta = [3][S, H, L] fp32 WORKSPACE (ABI 5; it was [S, H, L]): the dQ

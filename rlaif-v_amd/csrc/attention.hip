@@ -290,7 +290,15 @@ struct TileDma {
 // (rounds 1-4).  NW = 8: 256 queries, ONE workgroup per CU - every K / V tile is staged once per 256 queries, i.e. HALF the LDS-DMA
 // instructions per CU and key tile (each wave issues 4 instead of 8): the phase stamps of round 4 put 18 % of a tile in those issues,
 // which the CU's address path serves one wave-instruction at a time (profiles/r04_attn_fwd_dq_phase_profile.log).
-template <int HD, bool CAUSAL, int NW = 4>
+// MASK POLICY.  BRANCHES = false: the packed pair's window [sh, e1) with one e1 per row (rv_attn_fwd).  BRANCHES = true (always
+// causal; rv_attn_fwd_branches launches <HD, true, 4, true>): row s holds [shared prefix | branch 0 | ... | branch N-1] and
+// `seg_e1` is q_lo, one entry per TOKEN row of the buffer (tok0 + i): the first key of query i's own branch, relative to the row's
+// first token and non-decreasing inside a row (the host plan builder checks that, the kernel does not).  Query i hides the keys
+// [sh, q_lo[i]), i.e. every bound below takes its e1 from the query it speaks about: the lane's own query (element mask), the
+// block's first query (key tiles nobody in the block sees - q_lo does not decrease, so they are hidden from all its queries),
+// the wave's first query (tiles the wave skips), the wave's last query (the widest window of the wave: need_mask) and, for the
+// ranking of pair_blocks, the first query of block `lane`.  A query of the prefix (i < sh) has no window: its e1 is sh.
+template <int HD, bool CAUSAL, int NW = 4, bool BRANCHES = false>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(const bf16_t* __restrict__ qkv, long ld, int q_col0,
                                                            int k_col0, int v_col0, bf16_t* __restrict__ out, long ldo,
                                                            float* __restrict__ lse, int Lmax, int H, int nx, float scale,
@@ -298,6 +306,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
                                                            const int* __restrict__ seg_e1, int kv_group,
                                                            const int* __restrict__ row_off,
                                                            const int* __restrict__ row_len) {
+  static_assert(CAUSAL || !BRANCHES, "the branch mask is defined on top of the causal one");
   constexpr int KS = HD / 16, ET = HD / 32, TILE = 64 * HD * 2, STAGE = 2 * TILE;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -314,7 +323,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
   const int nqb = (L + BQ - 1) / BQ;
   if (varlen_done(bx, nqb, CAUSAL && !((nx >> 21) & 1))) return;
   // packed (chosen | rejected) rows: queries at index >= e1 (the rejected branch) do not see keys in [sh, e1)
-  const int sh = seg_sh ? seg_sh[s] : 0, e1 = seg_e1 ? seg_e1[s] : 0;
+  const int sh = seg_sh ? seg_sh[s] : 0, e1 = BRANCHES ? 0 : (seg_e1 ? seg_e1[s] : 0);
+  const int* qlo = BRANCHES ? seg_e1 + tok0 : nullptr;
+  auto e1_of = [&](int qq) { return qq >= sh ? qlo[min(qq, L - 1)] : sh; };
   const float c = scale * LOG2E;
 
   TileDma<HD, NW> dma;
@@ -328,7 +339,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
   const bf16_t* vbase = qkv + v_col0 + (h / kv_group) * HD;
 
   int blk_first, blk_second;
-  pair_blocks<false, BQ>(bx, nqb, L, sh, e1, lane, CAUSAL && ((nx >> 20) & 1), CAUSAL && ((nx >> 21) & 1), blk_first, blk_second);
+  if constexpr (BRANCHES)
+    pair_blocks<false, BQ>(bx, nqb, L, sh, lane < nqb ? e1_of(lane * BQ) : sh, lane, (nx >> 20) & 1, (nx >> 21) & 1, blk_first,
+                           blk_second);
+  else
+    pair_blocks<false, BQ>(bx, nqb, L, sh, e1, lane, CAUSAL && ((nx >> 20) & 1), CAUSAL && ((nx >> 21) & 1), blk_first, blk_second);
   const int npass = CAUSAL ? 2 : 1;
   for (int pass = 0; pass < npass; ++pass) {
     const int qb = (pass == 0) ? blk_first : blk_second;
@@ -336,7 +351,15 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
     const int q0 = qb * BQ, q0w = q0 + wave * 32;
     const int q = q0w + fr;
     QueryLaneMask<CAUSAL> qmask;
-    qmask.init(q, L, sh, e1);
+    int e1b = e1, e1w = e1, e1m = e1;             // e1 of the block's / the wave's first query and of the wave's last query
+    if constexpr (BRANCHES) {
+      e1b = __builtin_amdgcn_readfirstlane(e1_of(q0));
+      e1w = __builtin_amdgcn_readfirstlane(e1_of(q0w));
+      e1m = __builtin_amdgcn_readfirstlane(e1_of(q0w + 31));
+      qmask.init(q, L, sh, e1_of(q));
+    } else {
+      qmask.init(q, L, sh, e1);
+    }
 
     bf16x8_t qf[KS];
     {
@@ -355,8 +378,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
     // branch [sh, e1): those tiles are not fetched at all (block-uniform: DMA and barriers are workgroup-wide).  The loop
     // runs over the nte remaining tiles; the LDS stage alternates with the loop index, not the tile index.
     int skip_lo = nt, skip_n = 0;
-    if (q0 >= e1 && e1 > sh) {
-      const int lo = (sh + 63) >> 6, hi = e1 >> 6;
+    if (q0 >= e1b && e1b > sh) {
+      const int lo = (sh + 63) >> 6, hi = e1b >> 6;
       if (hi > lo) { skip_lo = lo; skip_n = hi - lo; }
     }
     const int nte = nt - skip_n;
@@ -375,7 +398,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
         dma.issue(kbase, ld, tok0, kn, L, smem + ((i + 1) & 1) * STAGE, wave);
         dma.issue(vbase, ld, tok0, kn, L, smem + ((i + 1) & 1) * STAGE + TILE, wave);
       }
-      if (!(CAUSAL && k0 > q0w + 31) && !(q0w >= e1 && k0 >= sh && k0 + 63 < e1)) {
+      if (!(CAUSAL && k0 > q0w + 31) && !(q0w >= e1w && k0 >= sh && k0 + 63 < e1w)) {
         // S^T = K Q^T.  The K fragments are fetched in groups of four explicit ds_read_b128, group g+1 in flight while
         // group g multiplies (the compiler's own schedule was read / wait / MFMA sixteen times per tile).  Fragment ks of
         // a row sits at chunk (2 ks + half) ^ swz(row): address = address(ks = 0) ^ (ks << 5).
@@ -409,7 +432,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd2_kernel(con
         // The tile needs element masks only when it touches the sequence end, the causal diagonal of this wave
         // or the chosen-branch window of a packed pair; interior tiles (the vast majority) skip ~200 VALU ops.
         const bool need_mask = (k0 + 63 >= L) || (CAUSAL && k0 + 63 > q0w) ||
-                               (q0w + 31 >= e1 && k0 + 63 >= sh && k0 < e1);
+                               (q0w + 31 >= e1m && k0 + 63 >= sh && k0 < e1m);
         if (need_mask) {
           qmask.apply(sacc[0], k0 + 4 * half);
           qmask.apply(sacc[1], k0 + 32 + 4 * half);
@@ -1488,6 +1511,39 @@ int rv_attn_fwd(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, vo
   } else if (hd == 128) { if (causal) LAUNCH_FWD(128, true); else LAUNCH_FWD(128, false); }
   else { if (causal) LAUNCH_FWD(64, true); else LAUNCH_FWD(64, false); }
 #undef LAUNCH_FWD
+  RV_CHECK_LAUNCH();
+  return 0;
+}
+
+int rv_attn_fwd_branches(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, void* out, long ldo, float* lse, int S,
+                         int L, int H, int hd, float scale, const int* seg_sh, const int* q_lo, int kv_group, const int* row_off,
+                         const int* row_len, void* stream) {
+  RV_REQUIRE(hd == 64 || hd == 128, "rv_attn_fwd_branches: head dim must be 64 or 128");
+  RV_REQUIRE(seg_sh != nullptr && q_lo != nullptr, "rv_attn_fwd_branches: seg_sh and q_lo are required");
+  RV_REQUIRE((row_off == nullptr) == (row_len == nullptr), "rv_attn_fwd_branches: row_off and row_len go together");
+  RV_REQUIRE(kv_group >= 1 && H % kv_group == 0, "rv_attn_fwd_branches: kv_group must divide the number of query heads");
+  RV_REQUIRE(ld % 8 == 0 && ldo % 8 == 0 && q_col0 % 8 == 0 && k_col0 % 8 == 0 && v_col0 % 8 == 0,
+             "rv_attn_fwd_branches: alignment");
+  RV_REQUIRE((double)L * (double)ld * 2.0 < 4.0e9,
+             "rv_attn_fwd_branches: one sequence must span < 4 GB of the qkv buffer (32-bit DMA offsets)");
+  if (S == 0 || L == 0) return 0;
+  // 128-query workgroups, the nx blocks of an (s, h) on one XCD, ranked block pairs: rv_attn_fwd's defaults
+  const int nb = (L + 127) / 128, nxr = (nb + 1) / 2;
+  const int nx = nxr | (1 << 16) | (1 << 20);
+  dim3 grid(nxr * H * S), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (hd == 128) {
+    static bool attr_done = false;
+    if (!attr_done) {
+      hipFuncSetAttribute((const void*)attn_fwd2_kernel<128, true, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+      attr_done = true;
+    }
+    hipLaunchKernelGGL((attn_fwd2_kernel<128, true, 4, true>), grid, block, 4 * 64 * 128 * 2, st, (const bf16_t*)qkv, ld, q_col0, k_col0,
+                       v_col0, (bf16_t*)out, ldo, lse, L, H, nx, scale, seg_sh, q_lo, kv_group, row_off, row_len);
+  } else {
+    hipLaunchKernelGGL((attn_fwd2_kernel<64, true, 4, true>), grid, block, 4 * 64 * 64 * 2, st, (const bf16_t*)qkv, ld, q_col0, k_col0,
+                       v_col0, (bf16_t*)out, ldo, lse, L, H, nx, scale, seg_sh, q_lo, kv_group, row_off, row_len);
+  }
   RV_CHECK_LAUNCH();
   return 0;
 }

@@ -932,6 +932,86 @@ __global__ void logp_finish_unpack_kernel(const float* __restrict__ pmax, const 
   }
 }
 
+// ------------------------------------------------------------------ next-token scores (yes / no feedback scoring)
+// One workgroup per row of fp32 logits: softmax over the columns [0, V_valid) after HF's RepetitionPenaltyLogitsProcessor (a logit
+// of a token id the prompt contains becomes l / penalty if l > 0, else l * penalty), read at the K wanted ids, plus lse and the
+// argmax (lowest index among equal maxima).  The prompt's ids are a bitmap in LDS (V_valid / 8 bytes), so the row is read ONCE
+// with an online softmax per thread; the partial (max, sum, argmax) triples are combined in a fixed order: deterministic.
+struct NtsPart {
+  float mx, sum;
+  int idx;
+};
+__device__ __forceinline__ NtsPart nts_combine(const NtsPart& a, const NtsPart& b) {
+  NtsPart r;
+  r.mx = fmaxf(a.mx, b.mx);
+  r.idx = (b.mx > a.mx || (b.mx == a.mx && b.idx < a.idx)) ? b.idx : a.idx;
+  const float fa = (a.mx == -INFINITY) ? 0.f : expf(a.mx - r.mx), fb = (b.mx == -INFINITY) ? 0.f : expf(b.mx - r.mx);
+  r.sum = a.sum * fa + b.sum * fb;
+  return r;
+}
+__device__ __forceinline__ float nts_penalised(float l, bool seen, float penalty) {
+  return seen ? (l > 0.f ? l / penalty : l * penalty) : l;
+}
+
+__global__ __launch_bounds__(256) void next_token_scores_kernel(const float* __restrict__ logits, long ldl, int V_valid,
+                                                                const int* __restrict__ seen_off,
+                                                                const int* __restrict__ seen_ids, float penalty,
+                                                                const int* __restrict__ want_ids, int K,
+                                                                float* __restrict__ probs, float* __restrict__ logp,
+                                                                int* __restrict__ argmax, float* __restrict__ lse) {
+  extern __shared__ uint32_t nts_bits[];          // [ceil(V_valid / 32)] when the penalty is on
+  __shared__ NtsPart part[4];
+  __shared__ float row_lse;
+  const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* row = logits + (long)m * ldl;
+  const bool pen = seen_off != nullptr && penalty != 1.0f;
+  if (pen) {
+    const int nw = (V_valid + 31) >> 5;
+    for (int i = tid; i < nw; i += 256) nts_bits[i] = 0u;
+    __syncthreads();
+    for (int i = seen_off[m] + tid; i < seen_off[m + 1]; i += 256) {
+      const int id = seen_ids[i];
+      if (id >= 0 && id < V_valid) atomicOr(&nts_bits[id >> 5], 1u << (id & 31));
+    }
+    __syncthreads();
+  }
+  auto value = [&](int i) { return nts_penalised(row[i], pen && ((nts_bits[i >> 5] >> (i & 31)) & 1u), penalty); };
+  NtsPart a = {-INFINITY, 0.f, 0x7fffffff};
+  for (int i = tid; i < V_valid; i += 256) {
+    const float l = value(i);
+    if (l > a.mx) {                                // indices grow inside a thread: the first of equal maxima stays
+      a.sum = (a.mx == -INFINITY ? 0.f : a.sum * expf(a.mx - l)) + 1.f;
+      a.mx = l;
+      a.idx = i;
+    } else if (l != -INFINITY) {
+      a.sum += expf(l - a.mx);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    NtsPart b;
+    b.mx = __shfl_xor(a.mx, o, 64);
+    b.sum = __shfl_xor(a.sum, o, 64);
+    b.idx = __shfl_xor(a.idx, o, 64);
+    a = (lane & o) ? nts_combine(b, a) : nts_combine(a, b);      // both lanes of a pair evaluate the same expression
+  }
+  if (lane == 0) part[wave] = a;
+  __syncthreads();
+  if (tid == 0) {
+    NtsPart r = nts_combine(nts_combine(part[0], part[1]), nts_combine(part[2], part[3]));
+    row_lse = r.mx + logf(r.sum);
+    lse[m] = row_lse;
+    argmax[m] = r.idx;
+  }
+  __syncthreads();
+  for (int k = tid; k < K; k += 256) {
+    const int id = want_ids[k];
+    const float lp = (id >= 0 && id < V_valid) ? value(id) - row_lse : -INFINITY;
+    logp[(long)m * K + k] = lp;
+    probs[(long)m * K + k] = expf(lp);
+  }
+}
+
 // per sequence: sum of its selected rows' logp (rows of sequence s are seq_off[s]..seq_off[s+1]),
 // fixed summation order -> deterministic.   out_sum[s], out_cnt[s]
 __global__ void seq_sum_kernel(const float* __restrict__ logp, const float* __restrict__ weight,
@@ -1463,6 +1543,23 @@ int rv_logp_finish_unpack(const float* pmax, const float* psum, const float* tgt
   RV_REQUIRE((per_token || n_per_token == 0) && (compact || n_compact == 0), "rv_logp_finish_unpack: NULL output with a non-zero size");
   hipLaunchKernelGGL(logp_finish_unpack_kernel, dim3((M + 3) / 4), dim3(256), 0, STREAM(stream), pmax, psum, tgt_logit, nblk,
                      M, dst_a, dst_b, dst_c, per_token, n_per_token, compact, n_compact);
+  RV_CHECK_LAUNCH();
+  return 0;
+}
+
+int rv_next_token_scores(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids,
+                         float penalty, const int* want_ids, int K, float* probs, float* logp, int* argmax, float* lse,
+                         void* stream) {
+  if (M == 0) return 0;
+  RV_REQUIRE(M > 0 && V_valid > 0 && ldl >= V_valid && K >= 0, "rv_next_token_scores: M, V_valid > 0, ldl >= V_valid, K >= 0");
+  RV_REQUIRE(logits && argmax && lse && (K == 0 || (want_ids && probs && logp)), "rv_next_token_scores: NULL buffer");
+  RV_REQUIRE(penalty > 0.f, "rv_next_token_scores: the repetition penalty must be positive (1 = off)");
+  RV_REQUIRE(seen_off == nullptr || seen_ids != nullptr, "rv_next_token_scores: seen_off without seen_ids");
+  const bool pen = seen_off != nullptr && penalty != 1.0f;
+  const size_t lds = pen ? (size_t)((V_valid + 31) / 32) * 4 : 0;
+  RV_REQUIRE(lds <= 60000, "rv_next_token_scores: the seen-id bitmap (V_valid / 8 bytes) must fit in LDS");
+  hipLaunchKernelGGL(next_token_scores_kernel, dim3(M), dim3(256), lds, STREAM(stream), logits, ldl, V_valid, seen_off,
+                     seen_ids, penalty, want_ids, K, probs, logp, argmax, lse);
   RV_CHECK_LAUNCH();
   return 0;
 }

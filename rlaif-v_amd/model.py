@@ -28,7 +28,7 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 import torch
 
 from . import ops
-from .splice import SplicePlan, build_packed_plan, build_splice_plan
+from .splice import SplicePlan, build_branch_plan, build_packed_plan, build_splice_plan
 
 BF16 = torch.bfloat16
 VT = "model.vision_tower.vision_tower.vision_model."
@@ -884,7 +884,8 @@ class LlavaDPOModel:
         else:
             qkv, s_qkv = self._proj_fwd(xn, i, "qkv", xd=xnd)
             ops.rope_inplace(qkv, cos, sin, L, H + cfg.n_kv_heads, hd, pos=plan.pos)      # q heads then k heads
-        attn, lse = ops.attn_fwd(qkv, S, L, H, hd, True, 0, d, d + cfg.kv_dim, seg=plan.seg, kv_group=cfg.kv_group, rows=plan.rows)
+        attn, lse = ops.attn_fwd(qkv, S, L, H, hd, True, 0, d, d + cfg.kv_dim, seg=plan.seg, kv_group=cfg.kv_group, rows=plan.rows,
+                                 branches=plan.branches)
         if self.resid_fp32:
             o, s_o = self._proj_fwd(attn, i, "o", residual=None)          # the BRANCH, bf16
             x_mid, xn2, rstd2 = ops.add_rmsnorm_fwd(x, o, st.p(f"layers.{i}.ln2"), cfg.rms_eps)   # fp32 stream + norm, one pass
@@ -1044,6 +1045,58 @@ class LlavaDPOModel:
         return StepOutput(loss=None, scalars=None, per_pair=None, seq_logp=seq_logp, seq_cnt=seq_cnt,
                           per_token_logp=per_token, plan=plan)
 
+    # ------------------------------------------------------------------ yes / no feedback scoring
+    def forward_next_token_scores(self, prompts, images, want_ids, packed: bool = True, repetition_penalty: float = 1.0,
+                                  max_row_tokens: Optional[int] = None):
+        """The labeler's side of the AI-feedback stage (muffin/llava15_gen_data.py:266-333, omnilmm/omnilmm_gen_data.py:245-300
+        with --is_yesno): ``generate(max_new_tokens=1, output_scores=True)`` per question, of which only softmax(scores[0]) at a
+        few token ids and the greedy token are kept - one prefill per question, no cache, no decode loop.
+        ``prompts[k]``: the full prompts (1-D input_ids with the image placeholder, as ``question_process`` builds them) of the
+        questions about ``images[k]``.  ``encode_images`` runs once per image.  ``packed``: the questions of an image share its
+        [system prompt | image | ...] prefix, computed once (splice.build_branch_plan, rv_attn_fwd_branches); ``packed=False``:
+        one plain causal pad-free row per question on the existing attention kernel (the comparison path).
+        ``repetition_penalty``: HF's RepetitionPenaltyLogitsProcessor over each question's own prompt ids - what
+        ``generate(input_ids=..., repetition_penalty=...)`` applies at the first step.  The reference's scripts end up WITHOUT it:
+        llava15_gen_data.py sets none, omnilmm_gen_data.py passes 1.1 to ``generate_vllm``, which generates from ``inputs_embeds``
+        alone (omnilmm/model/omnilmm.py:371-396), i.e. from an empty id tensor with nothing to penalise.  Default 1.0 = off.
+        Forward only, eval mode.  Returns (probs [n_q, K], logp [n_q, K], argmax int32 [n_q], lse [n_q]) on the
+        device, questions in input order (image by image)."""
+        cfg, st = self.cfg, self.store
+        if len(prompts) != len(images):
+            raise ValueError(f"{len(prompts)} prompt lists for {len(images)} images")
+        was_training = self.training
+        self.eval()
+        try:
+            self._cur_drop_step = self._dropout_step
+            self._cur_drop = self._resolve_lora_drop()
+            plan = build_branch_plan(prompts, cfg.n_image_tokens, cfg.model_max_length, splicer=self._row_splicer(),
+                                     pad_free=self.pad_free or not packed, max_row_tokens=max_row_tokens, packed=packed)
+            plan = plan.to(self.device)
+            feats = self.encode_images(images)
+            x = ops.splice_fwd(plan.src, st.p("model.embed_tokens.weight"), feats, cfg.hidden)
+            if self.resid_fp32:
+                x = ops.cast_bf16_to_f32(x)
+            cos, sin = self._rope(plan.L)
+            for i in range(cfg.layers):
+                x, _ = self._layer_fwd(i, x, plan, cos, sin, False)
+            if isinstance(x, tuple):
+                x = ops.add_f32_bf16(*x)
+            n_q = plan.n_seq
+            hsel = torch.zeros(max(64, ops.round_up(n_q, 64)), cfg.hidden, dtype=BF16, device=self.device)
+            ops.rmsnorm_fwd(x, st.p("model.norm.weight"), cfg.rms_eps, row_idx=plan.last_idx, out=hsel[:n_q], want_rstd=False)
+            logits = ops.gemm_nt_f32(hsel, st.p("lm_head.weight"))
+            seen = None
+            if repetition_penalty != 1.0:
+                uniq = [torch.unique(ids.cpu().long()) for plist in prompts for ids in plist]
+                uniq = [u[(u >= 0) & (u < cfg.vocab)] for u in uniq]
+                off = torch.zeros(n_q + 1, dtype=torch.int32)
+                off[1:] = torch.cumsum(torch.tensor([u.numel() for u in uniq]), 0).to(torch.int32)
+                seen = (off.to(self.device), torch.cat(uniq).to(torch.int32).to(self.device))
+            want = torch.as_tensor(want_ids, dtype=torch.int32).reshape(-1).to(self.device)
+            return ops.next_token_scores(logits, n_q, cfg.vocab, want, seen=seen, penalty=float(repetition_penalty))
+        finally:
+            self.train(was_training)
+
     # ------------------------------------------------------------------ backward
     def backward(self, out: StepOutput, coef: torch.Tensor):
         """coef[2B] = d loss / d seq_logp (rv_dpo_loss).  Fills ``store.flat_g`` (overwrites)."""
@@ -1163,7 +1216,7 @@ class LlavaDPOModel:
         x = inputs_embeds.to(self.device, BF16).reshape(S * L, d).contiguous()
         if self.resid_fp32:
             x = ops.cast_bf16_to_f32(x)
-        plan = SimpleNamespace(S=S, L=L, pos=None, seg=None, rows=None)
+        plan = SimpleNamespace(S=S, L=L, pos=None, seg=None, rows=None, branches=None)
         cos, sin = self._rope(L)
         self._cur_drop = self._resolve_lora_drop()
         for i in range(cfg.layers):

@@ -652,14 +652,28 @@ def gelu_bwd(dy, x):
 # ------------------------------------------------------------------------------------- attention
 def attn_fwd(qkv: torch.Tensor, S: int, L: int, H: int, hd: int, causal: bool, q_col0: int, k_col0: int,
              v_col0: int, out: Optional[torch.Tensor] = None, seg: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-             kv_group: int = 1, rows: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+             kv_group: int = 1, rows: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+             branches: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
     """Returns (out [tokens, H*hd], lse [S,H,L]).  kv_group > 1: grouped-query attention (H / kv_group key/value heads).
     ``rows`` = (row_off, row_len) int32 [S]: PAD-FREE rows - sequence s occupies token rows [row_off[s], row_off[s] + row_len[s])
-    of qkv, L is the maximum row length; None: S rectangular rows of L tokens."""
+    of qkv, L is the maximum row length; None: S rectangular rows of L tokens.
+    ``branches`` = (seg_sh int32 [S], q_lo int32 [token rows]): N-branch rows [shared prefix | branch 0 | ... | branch N-1]
+    (rv_attn_fwd_branches; causal, forward only).  The caller guarantees the q_lo conditions (splice.check_branch_rows)."""
     _chk2d(qkv, "qkv")
     if out is None:
         out = torch.empty(qkv.shape[0] if rows is not None else S * L, H * hd, dtype=BF16, device=qkv.device)
     lse = torch.empty(S, H, L, dtype=torch.float32, device=qkv.device)
+    if branches is not None:
+        if not causal or seg is not None:
+            raise ValueError("attn_fwd: branches is a causal mask of its own (no seg, causal=True)")
+        seg_sh, q_lo = branches
+        n_tok = qkv.shape[0] if rows is not None else S * L
+        for name, t, n in (("seg_sh", seg_sh, S), ("q_lo", q_lo, n_tok)):
+            if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or t.device != qkv.device:
+                raise ValueError(f"attn_fwd: branches {name} must be contiguous int32 [{n}] on {qkv.device}")
+        hip.call("rv_attn_fwd_branches", qkv, qkv.stride(0), q_col0, k_col0, v_col0, out, out.stride(0), lse, S, L, H, hd,
+                 1.0 / math.sqrt(hd), seg_sh, q_lo, int(kv_group), rows[0] if rows else None, rows[1] if rows else None)
+        return out, lse
     hip.call("rv_attn_fwd", qkv, qkv.stride(0), q_col0, k_col0, v_col0, out, out.stride(0), lse, S, L, H, hd,
              int(causal), 1.0 / math.sqrt(hd), seg[0] if seg else None, seg[1] if seg else None, int(kv_group),
              rows[0] if rows else None, rows[1] if rows else None)
@@ -700,6 +714,41 @@ def lmhead_logp_fwd(h: torch.Tensor, w: torch.Tensor, tgt: torch.Tensor, n_rows:
     hip.call("rv_lmhead_logp_fwd", h, h.stride(0), w, w.stride(0), tgt, n_rows, V, v_valid, h.shape[1], pmax, psum, tl, -1)
     hip.call("rv_logp_finish", pmax, psum, tl, nblk, n_rows, lse, logp)
     return logp, lse
+
+
+def next_token_scores(logits: torch.Tensor, n_rows: int, v_valid: int, want_ids: torch.Tensor,
+                      seen: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, penalty: float = 1.0):
+    """Softmax of the first ``n_rows`` rows of fp32 ``logits`` [rows, ld] over the columns [0, v_valid), read at ``want_ids``
+    (int32 [K]): returns (probs [n_rows, K], logp [n_rows, K], argmax int32 [n_rows], lse [n_rows]).  ``logits`` is not written.
+    ``seen`` = (seen_off int32 [n_rows + 1], seen_ids int32) with ``penalty`` != 1: HF's RepetitionPenaltyLogitsProcessor over
+    the token ids of each row's prompt."""
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1 or not logits.is_cuda:
+        raise ValueError("next_token_scores: logits must be a 2-D fp32 CUDA tensor with unit column stride")
+    if not (0 <= n_rows <= logits.shape[0] and 0 < v_valid <= logits.shape[1]):
+        raise ValueError(f"next_token_scores: {n_rows} rows x {v_valid} columns do not fit logits {tuple(logits.shape)}")
+    dev = logits.device
+    if want_ids.dtype != torch.int32 or want_ids.dim() != 1 or not want_ids.is_contiguous() or want_ids.device != dev:
+        raise ValueError("next_token_scores: want_ids must be contiguous int32 [K] on the logits' device")
+    if not penalty > 0.0:
+        raise ValueError("next_token_scores: the repetition penalty must be positive")
+    seen_off = seen_ids = None
+    if seen is not None and penalty != 1.0:
+        seen_off, seen_ids = seen
+        for name, t in (("seen_off", seen_off), ("seen_ids", seen_ids)):
+            if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"next_token_scores: {name} must be contiguous int32 on the logits' device")
+        if seen_off.numel() != n_rows + 1:
+            raise ValueError(f"next_token_scores: seen_off needs {n_rows + 1} entries")
+        if seen_ids.numel() == 0:                  # a NULL table would switch the penalty off by itself
+            seen_off = seen_ids = None
+    K = want_ids.numel()
+    probs = torch.empty(n_rows, K, dtype=torch.float32, device=dev)
+    logp = torch.empty(n_rows, K, dtype=torch.float32, device=dev)
+    argmax = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    lse = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    hip.call("rv_next_token_scores", logits, logits.stride(0), n_rows, v_valid, seen_off, seen_ids, float(penalty), want_ids, K,
+             probs, logp, argmax, lse)
+    return probs, logp, argmax, lse
 
 
 def gemm_auto_variant(M: int, N: int) -> int:

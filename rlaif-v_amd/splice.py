@@ -65,6 +65,9 @@ class SplicePlan:
     ev_len: Optional[List[int]] = None        # per sequence n_s - 1: the per-token entries it owns (n_s: spliced, truncated, pads dropped)
     ev_ld: int = 0                            # columns of the per-token matrix
     n_ev: int = 0
+    # N-branch rows of the yes / no feedback stage (build_branch_plan): row s = [shared prefix | tail 0 | tail 1 | ...]
+    q_lo: Optional[torch.Tensor] = None       # int32 [n_tokens] first key (relative to its row) of the token's own branch
+    last_idx: Optional[torch.Tensor] = None   # int32 [n_seq] buffer row of each question's last token, in input order
 
     def to(self, device) -> "SplicePlan":
         kw = {}
@@ -74,7 +77,12 @@ class SplicePlan:
 
     @property
     def seg(self):
-        return (self.seg_sh, self.seg_e1) if self.seg_sh is not None else None
+        return (self.seg_sh, self.seg_e1) if self.seg_sh is not None and self.q_lo is None else None
+
+    @property
+    def branches(self):
+        """(seg_sh, q_lo) for rv_attn_fwd_branches, None for every other layout."""
+        return (self.seg_sh, self.q_lo) if self.q_lo is not None else None
 
     @property
     def rows(self):
@@ -167,8 +175,9 @@ def make_omnilmm_splicer(im_patch: int, im_start: int, im_end: int):
     return splicer
 
 
-def _tables(flat: torch.Tensor, n_feat_rows: int):
-    """Embedding-backward segments and feature-gradient sources from the flat source table."""
+def _tables(flat: torch.Tensor, n_feat_rows: int, strict: bool = True):
+    """Embedding-backward segments and feature-gradient sources from the flat source table.  ``strict=False`` (forward-only
+    plans whose rows may repeat an image): a feature row with more than two users keeps its first two."""
     text_rows = torch.nonzero(flat >= 0, as_tuple=True)[0]
     text_ids = flat[text_rows]
     order = torch.sort(text_ids, stable=True).indices
@@ -191,7 +200,7 @@ def _tables(flat: torch.Tensor, n_feat_rows: int):
         first[1:] = fid_s[1:] != fid_s[:-1]
         second = torch.zeros_like(first)
         second[1:] = (~first[1:]) & first[:-1]
-        if bool((~(first | second)).any()):
+        if strict and bool((~(first | second)).any()):
             raise ValueError("an image feature row is used by more than two sequence positions; "
                              "the DPO path expects one image per (chosen, rejected) pair")
         a[fid_s[first]] = frow_s[first].to(torch.int32)
@@ -391,3 +400,136 @@ def build_packed_plan(input_ids: torch.Tensor, labels: torch.Tensor, n_img_token
                       row_off=torch.tensor(starts, dtype=torch.int32) if pad_free else None,
                       row_len=torch.tensor(lens, dtype=torch.int32) if pad_free else None,
                       w_sel=torch.cat(ws).contiguous() if token_weight is not None else None)
+
+
+def check_branch_rows(seg_sh: torch.Tensor, q_lo: torch.Tensor, starts: List[int], lens: List[int]) -> None:
+    """The conditions rv_attn_fwd_branches relies on and does not check: for every query i >= seg_sh[s] of row s (token row
+    starts[s] + i, i < lens[s]),  seg_sh[s] <= q_lo[i] <= i,  and q_lo does not decrease inside a row."""
+    n = int(q_lo.numel())
+    for s, (a, ln) in enumerate(zip(starts, lens)):
+        sh = int(seg_sh[s])
+        if not (ln >= 1 and 0 <= a and a + ln <= n):
+            raise ValueError(f"branch row {s}: token rows [{a}, {a + ln}) do not fit the q_lo table of {n} entries")
+        if not 0 <= sh <= ln:
+            raise ValueError(f"branch row {s}: shared prefix {sh} outside [0, {ln}]")
+        q = q_lo[a + sh:a + ln].long()
+        i = torch.arange(sh, ln)
+        if bool((q < sh).any()) or bool((q > i).any()):
+            raise ValueError(f"branch row {s}: q_lo must satisfy seg_sh <= q_lo[i] <= i for every query behind the prefix")
+        if bool((q[1:] < q[:-1]).any()):
+            raise ValueError(f"branch row {s}: q_lo decreases inside the row")
+
+
+def _splice_one(ids: torch.Tensor, image: int, n_img_tokens: int, splicer) -> torch.Tensor:
+    """One prompt spliced on its own (no truncation); its image-feature sources re-pointed at feature block ``image``."""
+    ids = ids.cpu().long().reshape(1, -1)
+    rows, _ = (splicer or _splice_rows)(ids, torch.full_like(ids, IGNORE_INDEX), n_img_tokens, 1, None)
+    src = rows[0]
+    return torch.where(src <= -2, src - image * n_img_tokens, src)
+
+
+def _shared_len(rows: List[torch.Tensor]) -> int:
+    """Longest common prefix of the spliced rows that leaves every row a token of its own and does not end inside an image
+    block (a run of consecutive feature sources).  A single row shares nothing: it is a plain causal row."""
+    if len(rows) == 1:
+        return 0
+    n = min(int(r.numel()) for r in rows)
+    eq = torch.ones(n, dtype=torch.bool)
+    for r in rows[1:]:
+        eq &= r[:n] == rows[0][:n]
+    ne = torch.nonzero(~eq)
+    sh = min(int(ne[0]) if ne.numel() else n, n - 1)
+
+    def cuts(k):       # the cut between k - 1 and k separates two features of one block in some row
+        return k > 0 and any(int(r[k - 1]) <= -2 and int(r[k]) == int(r[k - 1]) - 1 for r in rows)
+    while cuts(sh):
+        sh -= 1
+    return sh
+
+
+def build_branch_plan(prompts: List[List[torch.Tensor]], n_img_tokens: int, model_max_length: Optional[int], splicer=None,
+                      pad_free: bool = True, max_row_tokens: Optional[int] = None, packed: bool = True) -> SplicePlan:
+    """Forward-only plan of the yes / no feedback stage (muffin/llava15_gen_data.py:266-333, omnilmm/omnilmm_gen_data.py:245-300:
+    one prefill per question, only the next-token distribution behind the prompt is kept).
+    ``prompts[k]``: the full prompts (1-D input_ids with the image placeholder) of the questions about image k; image k's
+    features are feature rows [k * n_img_tokens, (k + 1) * n_img_tokens).
+    ``packed``: per image every prompt is spliced on its own, the rows' longest common prefix (never cutting an image block) is
+    kept once and the row is [prefix | tail 0 | tail 1 | ...]: under a causal mask a prefix position sees the same keys in every
+    stand-alone sequence, so its hidden states are shared; a tail token attends the prefix and its own tail (``seg_sh`` /
+    ``q_lo``, rv_attn_fwd_branches) and keeps the position it has in its stand-alone sequence (``pos``).  A row that would
+    exceed ``max_row_tokens`` is continued in a new row that carries the prefix again (a row always takes at least one tail).
+    ``packed=False``: one plain causal row per question (no seg_sh / q_lo: the existing attention kernel).
+    ``last_idx``: the buffer row of each question's last token, questions in input order (image by image).  A stand-alone
+    sequence longer than ``model_max_length`` raises ValueError (the stage scores complete prompts)."""
+    P = n_img_tokens
+    packed_src, packed_pos, packed_qlo, shs = [], [], [], []
+    last_rel: List[Tuple[int, int]] = []                                   # per question: (row, offset in the row)
+    for k, plist in enumerate(prompts):
+        if len(plist) == 0:
+            raise ValueError(f"image {k} has no question")
+        rows = [_splice_one(ids, k, P, splicer) for ids in plist]
+        for r in rows:
+            if r.numel() == 0:
+                raise ValueError(f"image {k}: empty prompt")
+            if model_max_length is not None and r.numel() > model_max_length:
+                raise ValueError(f"image {k}: a spliced prompt has {r.numel()} tokens, model_max_length is {model_max_length}")
+        if not packed:
+            for r in rows:
+                last_rel.append((len(packed_src), int(r.numel()) - 1))
+                packed_src.append(r)
+                packed_pos.append(torch.arange(r.numel()))
+            continue
+        sh = _shared_len(rows)
+        j = 0
+        while j < len(rows):
+            src, pos, qlo = [rows[0][:sh]], [torch.arange(sh)], [torch.zeros(sh, dtype=torch.int64)]
+            n = sh
+            while j < len(rows) and (n == sh or max_row_tokens is None or n + rows[j].numel() - sh <= max_row_tokens):
+                t = int(rows[j].numel()) - sh
+                src.append(rows[j][sh:])
+                pos.append(torch.arange(sh, sh + t))
+                qlo.append(torch.full((t,), n, dtype=torch.int64))
+                n += t
+                last_rel.append((len(packed_src), n - 1))
+                j += 1
+            packed_src.append(torch.cat(src))
+            packed_pos.append(torch.cat(pos))
+            packed_qlo.append(torch.cat(qlo))
+            shs.append(sh)
+    S = len(packed_src)
+    lens = [int(x.numel()) for x in packed_src]
+    L = max(lens)
+    if pad_free:
+        starts = [0] * S
+        for b in range(1, S):
+            starts[b] = starts[b - 1] + lens[b - 1]
+        n_tokens = starts[-1] + lens[-1]
+        flat, pos_flat = torch.cat(packed_src), torch.cat(packed_pos)
+        qlo_flat = torch.cat(packed_qlo) if packed else None
+    else:
+        starts = [b * L for b in range(S)]
+        n_tokens = S * L
+        src_full = torch.full((S, L), -1, dtype=torch.int64)
+        pos_full = torch.zeros((S, L), dtype=torch.int64)
+        qlo_full = torch.zeros((S, L), dtype=torch.int64)
+        for b in range(S):
+            src_full[b, :lens[b]], pos_full[b, :lens[b]] = packed_src[b], packed_pos[b]
+            if packed:                       # the pad queries behind a row continue its last branch (their results are not read)
+                qlo_full[b, :lens[b]] = packed_qlo[b]
+                qlo_full[b, lens[b]:] = packed_qlo[b][-1]
+        flat, pos_flat = src_full.reshape(-1), pos_full.reshape(-1)
+        qlo_flat = qlo_full.reshape(-1) if packed else None
+    seg_sh = torch.tensor(shs, dtype=torch.int32) if packed else None
+    q_lo = qlo_flat.to(torch.int32) if packed else None
+    if packed:
+        check_branch_rows(seg_sh, q_lo, starts, lens if pad_free else [L] * S)
+    last_idx = torch.tensor([starts[r] + o for r, o in last_rel], dtype=torch.int32)
+    uniq, seg_off, pos_sorted, a, bb = _tables(flat, max(len(prompts), 1) * P, strict=False)
+    e32 = torch.zeros(0, dtype=torch.int32)
+    n_q = len(last_rel)
+    return SplicePlan(S=S, L=L, n_seq=n_q, src=flat.to(torch.int32), labels=None, sel_idx=e32, tgt=e32,
+                      seq_off=torch.zeros(n_q + 1, dtype=torch.int32), seq_of_row=e32, uniq_ids=uniq, seg_off=seg_off,
+                      pos_sorted=pos_sorted, feat_src_a=a, feat_src_b=bb, n_sel=0, pos=pos_flat.to(torch.int32), seg_sh=seg_sh,
+                      shared_len=shs if packed else None, n_real_tokens=int(sum(lens)), n_tokens=n_tokens,
+                      row_off=torch.tensor(starts, dtype=torch.int32) if pad_free else None,
+                      row_len=torch.tensor(lens, dtype=torch.int32) if pad_free else None, q_lo=q_lo, last_idx=last_idx)

@@ -18,7 +18,7 @@ for f in sorted(glob.glob(os.path.join(d, "pmc_hot_*.txt"))):
 KEYS = ["gemm_nn_a64_kernel<EpiStore, false>", "gemm_nn_a64_kernel<EpiStore, false, true>", "gemm_nn_a64_kernel<EpiSwiGLU, false, true>",
         "gemm_nn_a64_kernel<EpiSwiGLUBwd, false, true>", "gemm_nt_256_kernel<EpiLogpFwd, true, false>",
         "gemm_nt_256_kernel<EpiLogpBwd, true, false>", "gemm_tn_256_kernel<EpiStoreF32, 3, true>", "gemm_tn_256_kernel<EpiStore, 3>",
-        "gemm_tn_256_kernel<EpiStore, 3, true>", "attn_fwd2_kernel<128, true>", "attn_fwd2_kernel<128, true, 4>",
+        "gemm_tn_256_kernel<EpiStore, 3, true>", "attn_fwd2_kernel<128, true>", "attn_fwd2_kernel<128, true, 4>", "attn_fwd2_kernel<128, true, 4, false>",
         "attn_bwd_dq2_kernel<true>", "attn_bwd_dkv3_kernel<true>", "attn_bwd_dkv2_kernel<true>"]
 for k in KEYS:
     if k not in tab:
