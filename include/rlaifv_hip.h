@@ -12,6 +12,10 @@
  *  - `ld*` are row strides in ELEMENTS; bf16 rows must be 16-byte aligned;
  *  - all work is enqueued on `stream` (a hipStream_t passed as void*); nothing synchronises;
  *  - return 0 = ok, 1 = argument error, 2 = launch error; text via rv_last_error() (thread local);
+ *  - containment (pinned by tests/test_containment_gpu.py): an entry point reads and writes only the logical [rows][cols] of its
+ *    operands - never the ld-padding columns behind a row, never a row past M / N / R (edge tiles of the GEMMs re-read the last
+ *    row, contraction rows past R of the TN forms come from an internal zero row), never a row that row_idx / idx / row_off +
+ *    row_len do not name - and no result depends on anything else; a workspace is written inside its documented size only;
  *  - no exceptions cross the ABI, no internal threads, no allocation.
  */
 #ifndef RLAIFV_HIP_H
@@ -192,7 +196,13 @@ int rv_gemm_nt_bf16_f32res(const void* A, long lda, const void* B, long ldb, flo
  *         tgt_logit[m] = logit of tgt[m].   V = rows of W = a multiple of 64; columns [V_valid, V) are vocabulary
  *         padding (a tokenizer with added tokens, e.g. OmniLMM's 32000 + 9): left out of the softmax, zero in dlogits.
  *   finish: lse[m], logp[m] = tgt_logit[m] - lse[m].
- *   bwd : dlogits[m][n] = coef[m] * ((n == tgt[m]) - exp(logit - lse[m]))  (bf16, recomputed logits). */
+ *   bwd : dlogits[m][n] = coef[m] * ((n == tgt[m]) - exp(logit - lse[m]))  (bf16, recomputed logits).
+ *   Sizes and padding: pmax / psum are [M][V / 64], written completely.  tgt_logit[m] is written only when 0 <= tgt[m] < V (-inf for
+ *   a target among the padding columns): the CALLER pre-fills it (ops.lmhead_logp_fwd: zeros), so a row whose target is no
+ *   vocabulary id (-100) gets logp = fill - lse and, in bwd, no one-hot term.  Rows of h past M are never read (h needs no padding rows for these calls) and rows
+ *   [V_valid, V) of W never reach a result.  bwd writes rows m < M of dlogits over all V columns (the padding columns as zeros)
+ *   and leaves rows >= M alone: a caller that feeds a row-padded dlogits to a GEMM zeroes those rows itself
+ *   (ops.lmhead_logp_bwd does). */
 int rv_lmhead_logp_fwd(const void* h, long ldh, const void* W, long ldw, const int* tgt, int M, int V, int V_valid, int K,
                        float* pmax, float* psum, float* tgt_logit, int variant, void* stream);
 int rv_logp_finish(const float* pmax, const float* psum, const float* tgt_logit, int nblk, int M, float* lse,
@@ -243,7 +253,12 @@ int rv_row_coef(const float* coef, const int* seq_of_row, const float* weight, f
  *   rows [row_off[s], row_off[s] + row_len[s]) of qkv / out (1 <= row_len[s] <= L); the reference right-pads every row to the batch
  *   maximum (llava/model/llava_arch.py:305-313) and SURVEY 8a property (i) makes skipping those pads exact.  L stays the MAXIMUM row
  *   length: it sizes the grid and the [S][H][L] stride of lse (and of the backward's delta planes); seg_sh / seg_e1 are per-row
- *   offsets as before.  Results of a row do not depend on where it starts (tiles are laid relative to the row's first token). */
+ *   offsets as before.  Results of a row do not depend on where it starts (tiles are laid relative to the row's first token).
+ *   What is touched: of qkv only the H (q) and H / kv_group (k, v) heads at the three column offsets, in the token rows of the S
+ *   sequences; of out (and of the backward's dqkv) only those rows and head columns - token rows between or behind pad-free
+ *   sequences and columns outside the heads are neither read nor written.  lse[s][h][l] is written for l < row_len[s] only; the
+ *   entries at l >= row_len[s] keep the caller's bytes and rv_attn_bwd does not read them; the per-token tables (q_lo, rope_pos)
+ *   are read at the sequences' token rows only. */
 int rv_attn_fwd(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, void* out, long ldo, float* lse, int S,
                 int L, int H, int hd, int causal, float scale, const int* seg_sh, const int* seg_e1, int kv_group,
                 const int* row_off, const int* row_len, void* stream);
@@ -269,7 +284,10 @@ int rv_attn_fwd_branches(const void* qkv, long ld, int q_col0, int k_col0, int v
  * rope_cos / rope_sin (fp32 [positions][64], both NULL = off) + rope_pos (int32 [S * L] position of every row, NULL = row
  * index inside its sequence): dQ and dK are written ALREADY rotated back (apply_rotary_pos_emb's autograd, HF
  * modeling_llama.py) - the separate rv_rope_inplace(backward) pass over dqkv is not needed.  rope_pos is indexed by the token's row
- * in the buffer (row_off[s] + i under pad-free rows, where it is required). */
+ * in the buffer (row_off[s] + i under pad-free rows, where it is required).
+ * The delta workspace needs no initialisation: each of its three [S][H][L] planes is written at l < row_len[s] (all l without
+ * pad-free rows) before the dK/dV kernel reads it there, the rest is neither written nor read, and nothing past
+ * rv_attn_bwd_workspace_floats(S, H, L) floats is touched.  dO and O are read like out is written (sequence rows, head columns). */
 int rv_attn_bwd(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, const void* dO, long lddo,
                 const void* O, long ldo, const float* lse, float* delta, void* dqkv, long lddq, int S, int L, int H,
                 int hd, int causal, float scale, const int* seg_sh, const int* seg_e1, int kv_group,
@@ -282,7 +300,11 @@ long rv_attn_bwd_workspace_floats(int S, int H, int L);
 int rv_attn_delta(const void* dO, long lddo, const void* O, long ldo, float* delta, int S, int L, int H, int hd,
                   void* stream);
 
-/* ---- norms / rotary / activations (replace HF LlamaRMSNorm, apply_rotary_pos_emb, LlamaMLP, CLIP LayerNorm) */
+/* ---- norms / rotary / activations (replace HF LlamaRMSNorm, apply_rotary_pos_emb, LlamaMLP, CLIP LayerNorm)
+ * row_idx (int32 [rows], NULL = identity) names the x row of output row r: x, and every operand that carries the residual stream
+ * (add / xout of rv_rmsnorm_fwd_f32, dres / dx of the backward forms), is indexed by row_idx[r]; y, yd, rstd and dy by r.  Rows of x
+ * that row_idx does not name are not read, rows of dx / xout it does not name are not written.  dw_partial is fp32 scratch
+ * [rv_rmsnorm_bwd_nblocks(rows)][d], written completely; dw is bf16 [d], written (dw_accumulate = 0) or read and added to. */
 int rv_rmsnorm_fwd(const void* x, long ldx, const int* row_idx, const void* w, void* y, long ldy, float* rstd,
                    int rows, int d, float eps, void* stream);
 int rv_rmsnorm_bwd_nblocks(int rows);   /* rows of the fp32 dw_partial scratch [nblocks][d] */
@@ -310,7 +332,8 @@ int rv_layernorm_fwd_f32in(const float* x, long ldx, const void* w, const void* 
 /* LayerNorm backward for the OmniLMM Resampler's trainable ln_q / ln_kv / ln_post (omnilmm/model/resampler.py:127-129,
  * autograd of F.layer_norm): dx (NULL = not wanted), dw / db written or accumulated.  x_period > 0: rows r and r + x_period
  * share the x row r % x_period (the learned queries, identical for every image).  partial: fp32 scratch
- * [rv_rmsnorm_bwd_nblocks(rows)][2 d]. */
+ * [rv_rmsnorm_bwd_nblocks(rows)][2 d].  Any d % 8 == 0 up to 8192: exactly d elements of dw and of db are written (or, with
+ * accumulate, read and written) - the two may be neighbours in one flat gradient buffer. */
 int rv_layernorm_bwd(const void* dy, long lddy, const void* x, long ldx, int x_period, const void* w, void* dx, long lddx,
                      float* partial, void* dw, void* db, int accumulate, int rows, int d, float eps, void* stream);
 /* y[r] = x[r] + p[r % period]: the Resampler's position tables added per image (resampler.py:150-155) */
@@ -355,11 +378,17 @@ int rv_resize_h_u8(const void* src, int H, int W, int y0, int rows, const int* b
 int rv_resize_v_norm_u8(const void* tmp, int rows, int out_w, const int* bounds, const int* kk, int ksize, int out_h,
                         const float* table, float* out, void* stream);
 
-/* ---- data movement */
+/* ---- data movement
+ * rv_transpose: out [C][ldo] = in [R][C] transposed, ldo >= roundup(R, 64), C % 8 == 0: row c of out holds in[:, c] in its columns
+ * [0, R) and ZEROS in the columns [R, roundup(R, 64)) (a K-padded GEMM operand); columns from roundup(R, 64) on are not written. */
 int rv_transpose(const void* in, long ld_in, void* out, long ldo, int R, int C, void* stream);
 /* prepare_inputs_labels_for_multimodal (llava/model/llava_arch.py:237-315): out row n = embed[src[n]] if
  * src[n] >= 0, zero if -1, image feature row (-2 - src[n]) otherwise. */
 int rv_splice_fwd(const int* src, const void* embed, const void* feats, void* out, long n_rows, int d, void* stream);
+/* rv_embed_bwd: row uniq_ids[u] of dW = the fp32 sum of the dx rows pos_sorted[seg_off[u] .. seg_off[u + 1]) (written, not added
+ * to); rows of dW that uniq_ids does not name are left alone (the caller zeroes dW).  rv_feat_grad: dfeat[r] = dx[src_a[r]] +
+ * dx[src_b[r]], an index of -1 = no such row.  rv_gather_rows: scatter = 0: out[r] = in[idx[r]]; 1: out[idx[r]] = in[r], rows of
+ * out that idx does not name are left alone. */
 int rv_embed_bwd(const int* uniq_ids, const int* seg_off, const int* pos_sorted, int n_uniq, const void* dx, void* dW,
                  int d, void* stream);
 int rv_feat_grad(const int* src_a, const int* src_b, const void* dx, void* dfeat, long n_rows, int d, void* stream);

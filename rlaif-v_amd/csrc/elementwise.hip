@@ -221,16 +221,17 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
   }
 }
 
-// out[c] (bf16) = sum_p partial[p][c]  (+ existing out if accumulate).  Block = 32 columns x 8 partial slices
+// out[c] (bf16) = sum_p partial[p][c]  (+ existing out if accumulate), c < d; rows of `partial` are `ldp` floats apart (ldp >= d:
+// the LayerNorm backward keeps two d-wide halves in one row).  Block = 32 columns x 8 partial slices
 // (fixed summation order -> deterministic); grid = d / 32 blocks instead of d / 256 single-column walkers.
-__global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __restrict__ partial, int nparts, int d,
+__global__ __launch_bounds__(256) void reduce_partials_kernel(const float* __restrict__ partial, int nparts, int d, int ldp,
                                                               bf16_t* __restrict__ out, int accumulate) {
   __shared__ float red[8][33];
   const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
   const int c = blockIdx.x * 32 + cl;
   float s = 0.f;
   if (c < d)
-    for (int p = sl; p < nparts; p += 8) s += partial[(long)p * d + c];
+    for (int p = sl; p < nparts; p += 8) s += partial[(long)p * ldp + c];
   red[sl][cl] = s;
   __syncthreads();
   if (sl == 0 && c < d) {
@@ -1198,7 +1199,7 @@ int rv_rmsnorm_bwd(const void* dy, long lddy, const void* x, long ldx, const int
                      (const bf16_t*)x, ldx, row_idx, (const bf16_t*)w, rstd, (const bf16_t*)dres, lddres,
                      (bf16_t*)dx, lddx, dw_partial, rows, d);
   RV_CHECK_LAUNCH();
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((d + 31) / 32), dim3(256), 0, STREAM(stream), dw_partial, nb, d,
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3((d + 31) / 32), dim3(256), 0, STREAM(stream), dw_partial, nb, d, d,
                      (bf16_t*)dw, dw_accumulate);
   RV_CHECK_LAUNCH();
   return 0;
@@ -1214,7 +1215,7 @@ int rv_rmsnorm_bwd_f32x(const void* dy, long lddy, const float* x, long ldx, con
   hipLaunchKernelGGL(rmsnorm_bwd_kernel<float>, dim3(nb), dim3(256), 0, STREAM(stream), (const bf16_t*)dy, lddy, x, ldx, row_idx,
                      (const bf16_t*)w, rstd, (const bf16_t*)dres, lddres, (bf16_t*)dx, lddx, dw_partial, rows, d);
   RV_CHECK_LAUNCH();
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((d + 31) / 32), dim3(256), 0, STREAM(stream), dw_partial, nb, d,
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3((d + 31) / 32), dim3(256), 0, STREAM(stream), dw_partial, nb, d, d,
                      (bf16_t*)dw, dw_accumulate);
   RV_CHECK_LAUNCH();
   return 0;
@@ -1273,11 +1274,11 @@ int rv_layernorm_bwd(const void* dy, long lddy, const void* x, long ldx, int x_p
   hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nb), dim3(256), 0, STREAM(stream), (const bf16_t*)dy, lddy, (const bf16_t*)x,
                      ldx, x_period, (const bf16_t*)w, (bf16_t*)dx, lddx, partial, rows, d, eps);
   RV_CHECK_LAUNCH();
-  // partial = [nb][2d] (gain | bias halves): one reduction over 2d columns, then the halves go to dw / db
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((d + 31) / 32), dim3(256), 0, STREAM(stream), partial, nb, 2 * d,
+  // partial = [nb][2d] (gain | bias halves): each half is reduced over its own d columns, rows 2d floats apart
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3((d + 31) / 32), dim3(256), 0, STREAM(stream), partial, nb, d, 2 * d,
                      (bf16_t*)dw, accumulate);
   RV_CHECK_LAUNCH();
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((d + 31) / 32), dim3(256), 0, STREAM(stream), partial + d, nb, 2 * d,
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3((d + 31) / 32), dim3(256), 0, STREAM(stream), partial + d, nb, d, 2 * d,
                      (bf16_t*)db, accumulate);
   RV_CHECK_LAUNCH();
   return 0;
