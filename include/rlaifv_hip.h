@@ -16,6 +16,10 @@
  *    operands - never the ld-padding columns behind a row, never a row past M / N / R (edge tiles of the GEMMs re-read the last
  *    row, contraction rows past R of the TN forms come from an internal zero row), never a row that row_idx / idx / row_off +
  *    row_len do not name - and no result depends on anything else; a workspace is written inside its documented size only;
+ *  - accuracy (pinned per element against float64 by tests/test_accuracy_gpu.py, bound and derivations in tests/accuracy.py): every
+ *    output is the documented formula evaluated in fp32 (any summation order; __expf / exp2, division, rsqrt, erff to a few fp32
+ *    ulps) and stored with ONE round-to-nearest-even; an operand is rounded to bf16 inside a kernel only where the entry point's
+ *    comment names that rounding ("ROUNDING:");
  *  - no exceptions cross the ABI, no internal threads, no allocation.
  */
 #ifndef RLAIFV_HIP_H
@@ -73,7 +77,8 @@ int rv_gemm_nn_bias_act_bf16(const void* A, long lda, const void* B, long ldb, v
  * llava/model/language_model/llava_llama.py:91-102): C = A B with B the W^T copy [K][N] of the fused q|k|v weight; the first
  * rope_cols columns (the q and k heads, head dim hd = 128) leave rotated - y1 = x1 cos - x2 sin, y2 = x2 cos + x1 sin for the
  * half-split pairs (i, i + 64), tables [position][64] fp32 as rv_rope_inplace takes them, position = pos[token] or token % L - from
- * the fp32 accumulators (one rounding; replaces rv_gemm_nn_bf16 + rv_rope_inplace).  N, rope_cols multiples of 256, K % 64 == 0. */
+ * the fp32 accumulators (one rounding; replaces rv_gemm_nn_bf16 + rv_rope_inplace).  N, rope_cols multiples of 256, K % 64 == 0,
+ * K >= 512. */
 int rv_gemm_nn_rope_bf16(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
                          const float* cos_tab, const float* sin_tab, const int* pos, int L, int rope_cols, int hd, void* stream);
 
@@ -97,7 +102,9 @@ int rv_gemm_nn_lora_swiglu_bwd_bf16(const void* A, long lda, const void* B, long
 int rv_gemm_nn_swiglu_bf16(const void* A, long lda, const void* B, long ldb, void* GU, long ldgu, void* ACT, long ldact,
                            int M, int N, int K, void* stream);
 /* Input gradient of down_proj with the SwiGLU backward in the epilogue: d act = A [M][K] x B [K][N] (B = W_down, N = ffn)
- * never reaches memory; DGU [M][2N] = d(gate|up) interleaved like GU [M][2N]. */
+ * never reaches memory; DGU [M][2N] = d(gate|up) interleaved like GU [M][2N].
+ * ROUNDING (this and rv_gemm_nn_lora_swiglu_bwd_bf16): d act is rounded to bf16 before SwiGLU' is applied (what the unfused path
+ * stores); the forward forms compute ACT from the fp32 accumulators (one rounding) and ACTD = rv_dropout of the ROUNDED ACT. */
 int rv_gemm_nn_swiglu_bwd_bf16(const void* A, long lda, const void* B, long ldb, const void* GU, long ldgu, void* DGU,
                                long lddgu, int M, int N, int K, void* stream);
 
@@ -165,7 +172,8 @@ int rv_gemm_nt_dropout_masks_bf16(const void* dT, long lddt, const void* AT, lon
 
 /* Adapter weight gradient: dA[64 g .. 64 g + 63][:] = dT_g^T dropout_{p, seed_g}(X), dT [R][64 G], X [R][K], dA [64 G][K], from
  * one pass over X: `splits` chunks of the token rows are reduced into fp32 slabs (workspace: splits * 64 G * K floats, caller
- * owned) which a second pass sums in a fixed order.  Deterministic.  K % 64 == 0; p = 0 is rv_gemm_tn_bf16_splitk. */
+ * owned) which a second pass sums in a fixed order.  Deterministic.  K % 64 == 0; p = 0 is rv_gemm_tn_bf16_splitk.
+ * ROUNDING: as in the down-projection, the kept values of X are scaled by 1.f / (1.f - p) and rounded to bf16 before the MFMA. */
 int rv_gemm_tn_lora_masks_bf16(const void* dT, long lddt, const void* X, long ldx, void* dA, long ldda, int R, int K, int G, float p,
                                int seed0, int seed1, int seed2, int splits, float* workspace, void* stream);
 
@@ -259,6 +267,10 @@ int rv_row_coef(const float* coef, const int* seq_of_row, const float* weight, f
  *   sequences and columns outside the heads are neither read nor written.  lse[s][h][l] is written for l < row_len[s] only; the
  *   entries at l >= row_len[s] keep the caller's bytes and rv_attn_bwd does not read them; the per-token tables (q_lo, rope_pos)
  *   are read at the sequences' token rows only. */
+/*   ROUNDING (rv_attn_fwd, rv_attn_fwd_branches): the probabilities p = exp2(scale log2e s - m) are rounded to bf16 for the P V MFMA;
+ *   the row sum (the denominator of out, and lse) is taken from the unrounded fp32 p.  rv_attn_bwd: P (for dV) and dS = P (dP - delta)
+ *   (for dQ, dK) are rounded to bf16 once, for their MFMAs; with rope_cos / rope_sin, dQ and dK are rounded to bf16 (what the
+ *   separate rv_rope_inplace pass read back) and then rotated in fp32, so they carry a second rounding at the store. */
 int rv_attn_fwd(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, void* out, long ldo, float* lse, int S,
                 int L, int H, int hd, int causal, float scale, const int* seg_sh, const int* seg_e1, int kv_group,
                 const int* row_off, const int* row_len, void* stream);
