@@ -438,6 +438,57 @@ int rv_grad_accum(float* acc, void* g, long n, int mode, float scale, void* stre
  *      doing the receive-reduce-send of a ring all-reduce step (script/zero2.json:16-22 is what the real exchange replaces). */
 int rv_reduce_copy_persistent(const void* a, const void* b, void* dst, long n, int n_wg, void* stream);
 
+/* ---- KV-cached candidate generation (csrc/decode.hip; additive, ABI stays 7).  Replaces the decode steps of HF
+ *      GenerationMixin.sample / greedy_search with use_cache=True behind model.generate(do_sample=True, temperature=, ...) in the
+ *      sampling branch of muffin/llava15_gen_data.py:335-357 and omnilmm/omnilmm_gen_data.py:305-323.
+ *
+ * rv_gemm_nt_skinny_bf16: the nn.Linear products of ONE decode step (q|k|v, o, gate|up, down, LM head), 1 <= M <= 64 rows:
+ *   C[m][n] = sum_k A[m][k] W[n][k] (+ residual[m][n]),  W [N][K] with K contiguous (rv_gemm_nt_bf16's orientation), fp32 accumulate.
+ *   K % 64 == 0, N % 4 == 0, lda / ldw % 8 == 0, ldc / ldr % 4 == 0.  out_f32: 0 = C is bf16, 1 = C is fp32 (the LM-head logits that
+ *   rv_next_token_scores / rv_sample_token read); residual is bf16 in both cases and may be NULL.  Weight-bandwidth bound: one
+ *   workgroup owns a 16-column panel and all M rows (256 workgroups at N = 4096), W goes from global memory straight into MFMA
+ *   fragments, the workgroup's 8 waves split K and are added in wave order through LDS; no split across workgroups.
+ *   PROPERTY (pinned by tests/test_decode_kernels_gpu.py): C[m][n] is a function of row m of A (and of residual) and row n of W
+ *   alone - bit-identical for the same row at M = 1 and at M = 64, whatever the other rows hold.
+ *   Containment: reads rows < M of A / residual and rows < N of W, columns < K (< N for residual); writes C[m][n] for m < M, n < N
+ *   only (edge tiles re-read the last row).  No operand is rounded inside the kernel; one rounding at the bf16 store. */
+int rv_gemm_nt_skinny_bf16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K,
+                           const void* residual, long ldr, int out_f32, void* stream);
+/* rv_attn_decode: attention of ONE query token per sequence against a cache (HF LlamaAttention with past_key_values, q_len = 1).
+ *   kv: bf16 [rows][ldkv], the cache of one layer: K head g at columns k_col0 + g*hd (RoPE already applied), V head g at v_col0 + g*hd.
+ *   Sequence m attends exactly the cache rows [pre_off[m], pre_off[m] + pre_len[m]) (the prompt; the samples of one prompt name the
+ *   same span, so it is stored once) followed by [own_off[m], own_off[m] + own_len[m]) (its own tokens, the current one included:
+ *   the caller appends it before the call).  pre_len[m] + own_len[m] >= 1 (CALLER's guarantee); either span may be empty.
+ *   q: bf16 [M][ldq], out: bf16 [M][ldo], head h at column h*hd; hd = 128; kv_group in {1, 2, 4, 8} as in rv_attn_fwd (query head h
+ *   reads kv head h / kv_group); lse (optional, fp32 [M][H]): natural log of sum exp(scale q.k).
+ *   One workgroup per (sequence, kv head, key split) serves the kv_group query heads of its kv head from one read of K / V (global
+ *   memory straight to registers); split s takes keys [s c, (s + 1) c), c = ceil((pre_len + own_len) / n_split), and writes
+ *   (m, l, partial O) to workspace; a second launch adds the n_split partials in split order - a split without keys has weight 0.
+ *   Deterministic for a given n_split; the result of a sequence does not depend on the other sequences of the call.
+ *   workspace: fp32, rv_attn_decode_workspace_floats(M, H, n_split) elements (0 for bad arguments), needs no initialisation.
+ *   Containment: of kv only the two spans' rows at the K / V head columns are read; q / out rows < M at the head columns.
+ *   ROUNDING: none inside - softmax and P V run in fp32 on the vector units (p is NOT rounded to bf16); out is rounded once. */
+long rv_attn_decode_workspace_floats(int M, int H, int n_split);
+int rv_attn_decode(const void* q, long ldq, const void* kv, long ldkv, int k_col0, int v_col0, const int* pre_off,
+                   const int* pre_len, const int* own_off, const int* own_len, void* out, long ldo, float* lse, int M, int H, int hd,
+                   int kv_group, float scale, int n_split, float* workspace, long workspace_floats, void* stream);
+/* rv_sample_token: one token per row from fp32 logits [M][ldl] over the columns [0, V_valid), V_valid <= 65536 (HF's processor order:
+ * RepetitionPenaltyLogitsProcessor, TemperatureLogitsWarper, TopPLogitsWarper, softmax, multinomial):
+ *   1. repetition penalty over seen_ids[seen_off[m] .. seen_off[m+1]) as in rv_next_token_scores (ids outside [0, V_valid) are
+ *      skipped; penalty == 1 or seen_off == NULL: off);   2. l / temperature;
+ *   3. top_p < 1: a token of probability v is dropped iff the probability mass of all tokens <= v is <= 1 - top_p (what the
+ *      warper's ascending sort + cumsum decides, found here by bisection over v with the row in registers); the top token always
+ *      stays; equal probabilities at the edge stay or go TOGETHER (HF's sort splits them arbitrarily); top_p >= 1 keeps all;
+ *   4. softmax over the kept set;   5. inverse CDF in vocabulary-index order: the first kept id whose running sum exceeds
+ *      u[m] * total, u[m] in [0, 1) supplied by the caller (a seeded torch.Generator on the host: reproducible, and tests plant u).
+ *   temperature == 0: greedy - the LOWEST index among equal maxima (rv_next_token_scores' argmax), u may be NULL, top_p is ignored
+ *   and logp is the log-softmax of the penalised logits at that token.
+ *   token int32 [M]; logp fp32 [M] = log-probability of the token under the final (kept, renormalised) distribution.
+ *   The DISTRIBUTION is HF's; the map from random numbers to tokens is this kernel's own - torch.multinomial's stream cannot be
+ *   reproduced.  One workgroup per row, fixed reduction order; logits are read only, inside [0, V_valid) of rows < M. */
+int rv_sample_token(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids, float penalty,
+                    float temperature, float top_p, const float* u, int* token, float* logp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

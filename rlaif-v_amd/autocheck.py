@@ -193,7 +193,8 @@ def main(argv=None):
     ap.add_argument("--unpacked", action="store_true", help="one plain causal row per question (the comparison path)")
     args = ap.parse_args(argv)
     if not args.is_yesno:
-        raise NotImplementedError("only --is_yesno (next-token scores) is implemented: open-ended generation is out of scope")
+        raise NotImplementedError("only --is_yesno (next-token scores) is implemented here: candidate answers come from "
+                                  "python -m rlaif_v_amd.gen_data")
     import transformers
     from .checkpoint import from_pretrained
     model = from_pretrained(args.checkpoint, with_optimizer=False)

@@ -1,0 +1,103 @@
+"""Candidate answers for the AI-feedback stage: the sampling side of the loop that makes the preference pairs.
+
+Mirrors (paths relative to the reference checkout) the non-``--is_yesno`` branch of
+  muffin/llava15_gen_data.py:335-381   (LLaVA-1.5, conv_llava_v1 prompts)
+started by script/data_gen/llava15/llava15_diverse_gen.sh with ``--repeat N --temperature 0.7 --max_tokens ...``: the dataset
+repeats every (image, question) item N times in a row (GenDataset, :102-106) and ``generate(do_sample=True, temperature=,
+max_new_tokens=, use_cache=True)`` answers each copy on its own - N prefills of the same prompt.  Here the N copies of an item
+are ONE prompt with ``repeat=N`` samples: the tower and the prefill run once, the prompt's keys and values are stored once and the
+N decode rows share them (LlavaDPOModel.generate, rv_gemm_nt_skinny_bf16, rv_attn_decode, rv_sample_token).
+
+Sampling: HF's distribution (temperature, then top_p when given), drawn from uniforms of a seeded CPU generator - ``--seed``
+fixes the output, but the stream is not torch.multinomial's, so the reference's exact samples are not reproduced (no two
+seeds of the reference agree either).  ``--num_beam`` >= 1 (the reference's beam-search branch) is not implemented.
+
+Records, one per repeat in the reference's order (item by item, the copies of an item in a row): question_id, ds_question_id (when
+metainfos carries one), raw_question, answer (the decoded new tokens, special tokens skipped, stripped), metainfos, model_path.
+
+Command line (the jsonl format of the reference's GenDataset in; one record per line out):
+    python -m rlaif_v_amd.gen_data --checkpoint CKPT --ds_name questions.jsonl --answer_file out.jsonl \\
+        --repeat 10 --temperature 0.7 --max_tokens 512 --seed 0
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+from typing import Dict, List, Optional, Sequence
+
+import torch
+
+from .autocheck import read_gen_dataset, wrap_question_for_llava15
+
+
+def generate_answers(model, tokenizer, items: Sequence[Dict], repeat: int = 1, temperature: float = 0.7, top_p: float = 1.0,
+                     max_tokens: int = 10, seed: Optional[int] = 0, prompts_per_call: int = 6, model_path: Optional[str] = None,
+                     repetition_penalty: float = 1.0) -> List[Dict]:
+    """``items``: dicts with ``question`` (text), ``image`` (what ``encode_images`` takes for ONE image: a preprocessed
+    [3, H, W] tensor or a raw uint8 [H, W, 3] image), optionally ``question_id`` (default: the item's index) and ``metainfos``.
+    ``repeat`` samples per item at ``temperature`` (0 = greedy: the copies are then equal); ``seed``: the CPU generator the
+    uniforms come from (None: torch's default generator).  ``prompts_per_call`` items share one ``generate`` call."""
+    if getattr(model.cfg, "arch", "llava") == "omnilmm":
+        raise NotImplementedError("gen_data: OmniLMM generation is not implemented (LlavaDPOModel.generate is LLaVA-1.5 only)")
+    gen = torch.Generator().manual_seed(int(seed)) if seed is not None else None
+    eos = getattr(tokenizer, "eos_token_id", None)
+    mm = getattr(model.cfg, "mm_use_im_start_end", False)
+    records: List[Dict] = []
+    step = max(1, prompts_per_call)
+    for i0 in range(0, len(items), step):
+        chunk = items[i0:i0 + step]
+        prompts = [wrap_question_for_llava15(it["question"], tokenizer, mm) for it in chunk]
+        images = [it["image"] for it in chunk]
+        if all(torch.is_tensor(im) for im in images) and len({(im.shape, im.dtype) for im in images}) == 1 \
+                and images[0].dtype != torch.uint8:
+            images = torch.stack(images)
+        out = model.generate(prompts, images, max_new_tokens=max_tokens, repeat=repeat, temperature=temperature, top_p=top_p,
+                             repetition_penalty=repetition_penalty, eos_token_id=eos, generator=gen)
+        for n, it in enumerate(chunk):
+            meta = it.get("metainfos", {})
+            for r in range(repeat):
+                rec = {"question_id": it.get("question_id", i0 + n)}
+                if "ds_question_id" in meta:
+                    rec["ds_question_id"] = meta["ds_question_id"]
+                rec.update(raw_question=it["question"], answer=tokenizer.decode(out[n][r], skip_special_tokens=True).strip(),
+                           metainfos=meta, model_path=model_path)
+                records.append(rec)
+    return records
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--checkpoint", type=str, required=True)
+    ap.add_argument("--ds_name", type=str, required=True, help="question file in the jsonl format of the reference's GenDataset")
+    ap.add_argument("--answer_file", type=str, required=True)
+    ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--temperature", type=float, default=0.7)
+    ap.add_argument("--top_p", type=float, default=1.0)
+    ap.add_argument("--max_tokens", type=int, default=10)
+    ap.add_argument("--num_beam", type=int, default=-1)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--batch_size", type=int, default=6, help="items per generate call (x --repeat decode rows)")
+    ap.add_argument("--start", "--start_pos", dest="start", type=int, default=0)
+    ap.add_argument("--end", "--end_pos", dest="end", type=int, default=-1)
+    args = ap.parse_args(argv)
+    if args.num_beam >= 1:
+        raise NotImplementedError("--num_beam >= 1 (beam search) is not implemented: only the sampling branch is")
+    import transformers
+    from .checkpoint import from_pretrained
+    model = from_pretrained(args.checkpoint, with_optimizer=False)
+    tokenizer = transformers.AutoTokenizer.from_pretrained(args.checkpoint, use_fast=False)
+    with open(os.path.join(args.checkpoint, "config.json")) as f:
+        aspect = json.load(f).get("image_aspect_ratio")
+    items = read_gen_dataset(args.ds_name, args.start, args.end, image_aspect_ratio=aspect)
+    records = generate_answers(model, tokenizer, items, repeat=args.repeat, temperature=args.temperature, top_p=args.top_p,
+                               max_tokens=args.max_tokens, seed=args.seed, prompts_per_call=args.batch_size,
+                               model_path=args.checkpoint)
+    with open(args.answer_file, "w") as f:
+        for rec in records:
+            f.write(json.dumps(rec) + "\n")
+    print(f"{len(records)} records -> {args.answer_file}")
+
+
+if __name__ == "__main__":
+    main()

@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import math
 import os
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
@@ -1094,6 +1094,178 @@ class LlavaDPOModel:
                 seen = (off.to(self.device), torch.cat(uniq).to(torch.int32).to(self.device))
             want = torch.as_tensor(want_ids, dtype=torch.int32).reshape(-1).to(self.device)
             return ops.next_token_scores(logits, n_q, cfg.vocab, want, seen=seen, penalty=float(repetition_penalty))
+        finally:
+            self.train(was_training)
+
+    # ------------------------------------------------------------------ KV-cached candidate generation
+    def _prefill(self, prompts, images, caches: Optional[List[torch.Tensor]] = None):
+        """One plain causal pad-free row per prompt through the existing forward (encode_images, splice, _layer_fwd: today's
+        bits).  Returns fp32 last-position logits [round_up(n, 64), vocab_padded] (rows >= n are the LM head of zero rows).
+        ``caches``: per layer a [rows, 2 kv_dim] bf16 buffer; the layer's roped K | V rows are copied to its first n_tokens rows."""
+        cfg, st = self.cfg, self.store
+        d = cfg.hidden
+        self._cur_drop_step = self._dropout_step
+        self._cur_drop = self._resolve_lora_drop()
+        plan = build_branch_plan([[p] for p in prompts], cfg.n_image_tokens, cfg.model_max_length, splicer=self._row_splicer(),
+                                 pad_free=True, packed=False).to(self.device)
+        feats = self.encode_images(images)
+        x = ops.splice_fwd(plan.src, st.p("model.embed_tokens.weight"), feats, d)
+        if self.resid_fp32:
+            x = ops.cast_bf16_to_f32(x)
+        cos, sin = self._rope(plan.L)
+        for i in range(cfg.layers):
+            x, lctx = self._layer_fwd(i, x, plan, cos, sin, caches is not None)
+            if caches is not None:
+                caches[i][:plan.n_tokens].copy_(lctx["qkv"][:, d:])      # device copy of the roped K | V columns (plumbing)
+                del lctx
+        if isinstance(x, tuple):
+            x = ops.add_f32_bf16(*x)
+        n = plan.n_seq
+        hsel = torch.zeros(max(64, ops.round_up(n, 64)), d, dtype=BF16, device=self.device)
+        ops.rmsnorm_fwd(x, st.p("model.norm.weight"), cfg.rms_eps, row_idx=plan.last_idx, out=hsel[:n], want_rstd=False)
+        return ops.gemm_nt_f32(hsel, st.p("lm_head.weight"))
+
+    def _decode_step(self, tok: torch.Tensor, pos: torch.Tensor, dst: torch.Tensor, spans, caches: List[torch.Tensor],
+                     n_split: int, out: torch.Tensor):
+        """One decode step of at most 64 sequences: token ids ``tok`` at RoPE positions ``pos``, their K | V appended at cache
+        rows ``dst``, attention over ``spans`` (current token included), fp32 logits into ``out`` [M, vocab_padded]."""
+        cfg, st = self.cfg, self.store
+        d, H, hd, kvd = cfg.hidden, cfg.heads, cfg.head_dim, cfg.kv_dim
+        cos, sin = self._rope_cache[1], self._rope_cache[2]
+        x = ops.gather_rows(st.p("model.embed_tokens.weight"), tok)
+        pending = None
+        if self.resid_fp32:
+            x = ops.cast_bf16_to_f32(x)
+        for i in range(cfg.layers):
+            if pending is not None:
+                x, xn, _ = ops.add_rmsnorm_fwd(x, pending, st.p(f"layers.{i}.ln1"), cfg.rms_eps)
+            else:
+                xn, _ = ops.rmsnorm_fwd(x, st.p(f"layers.{i}.ln1"), cfg.rms_eps, want_rstd=False)
+            qkv = ops.gemm_nt_skinny(xn, st.p(f"layers.{i}.wqkv"))
+            ops.rope_inplace(qkv, cos, sin, 1, H + cfg.n_kv_heads, hd, pos=pos)           # q heads then k heads
+            ops.scatter_rows(qkv[:, d:], dst, caches[i])
+            attn, _ = ops.attn_decode(qkv, caches[i], H, hd, 0, kvd, spans, kv_group=cfg.kv_group, n_split=n_split)
+            if self.resid_fp32:
+                o = ops.gemm_nt_skinny(attn, st.p(f"layers.{i}.wo"))
+                x, xn2, _ = ops.add_rmsnorm_fwd(x, o, st.p(f"layers.{i}.ln2"), cfg.rms_eps)
+            else:
+                x = ops.gemm_nt_skinny(attn, st.p(f"layers.{i}.wo"), residual=x)
+                xn2, _ = ops.rmsnorm_fwd(x, st.p(f"layers.{i}.ln2"), cfg.rms_eps, want_rstd=False)
+            gu = ops.gemm_nt_skinny(xn2, st.p(f"layers.{i}.wgu"))
+            act = ops.swiglu_fwd(gu, interleaved=st.interleave_gu)
+            if self.resid_fp32:
+                pending = ops.gemm_nt_skinny(act, st.p(f"layers.{i}.wdown"))
+            else:
+                x = ops.gemm_nt_skinny(act, st.p(f"layers.{i}.wdown"), residual=x)
+        if pending is not None:
+            x = ops.add_f32_bf16(x, pending)
+        h, _ = ops.rmsnorm_fwd(x, st.p("model.norm.weight"), cfg.rms_eps, want_rstd=False)
+        ops.gemm_nt_skinny(h, st.p("lm_head.weight"), out=out, out_f32=True)
+
+    def generate(self, prompts, images, max_new_tokens: int, repeat: int = 1, temperature: float = 0.0, top_p: float = 1.0,
+                 repetition_penalty: float = 1.0, eos_token_id: Optional[int] = None,
+                 generator: Optional[torch.Generator] = None, return_scores: bool = False, num_beams: int = 1, *,
+                 _uniforms: Optional[torch.Tensor] = None, _forced_tokens: Optional[torch.Tensor] = None):
+        """The sampling branch of the AI-feedback stage (muffin/llava15_gen_data.py:335-357: ``generate(do_sample=True,
+        temperature=, max_new_tokens=, use_cache=True)`` on a dataset that repeats every item ``--repeat`` times): ``repeat``
+        candidate answers per (image, prompt) with a KV cache.  ``prompts[k]``: 1-D input_ids with the image placeholder,
+        about ``images[k]``.  Prefill = the existing forward, one pad-free causal row per prompt, whose roped K | V rows become
+        the first rows of every layer's cache - stored ONCE per prompt, the ``repeat`` samples attend the same rows
+        (splice.plan_decode_rows).  Each decode step runs len(prompts) * repeat sequences (chunks of <= 64 rows) through
+        norm, rv_gemm_nt_skinny_bf16, RoPE, scatter into the cache, rv_attn_decode, SwiGLU and rv_sample_token; the loop is a
+        host ``for`` over at most ``max_new_tokens`` steps and the finished flags are read back every 8 steps.  A finished
+        sequence keeps its row and is decoded on until all are finished (its later tokens are dropped): with long answers of
+        very different lengths that is work for nothing, the price of fixed chunks and no device-side waiting.
+        ``temperature`` 0 = greedy; else HF's processor order (repetition penalty, temperature, top_p) with uniforms drawn on
+        the host from ``generator`` (a CPU torch.Generator; None = the default one): [max_new_tokens, n_seq] in one draw, so a
+        seed fixes the output.  The distribution is HF's, the stream is not torch.multinomial's.  The repetition penalty
+        covers the ids a sequence has GENERATED so far, no prompt id - the reference's generate starts from inputs_embeds, so
+        its processor sees no prompt id either (as forward_next_token_scores documents for the first token).  ``num_beams``
+        exists to refuse beam search by name.  Test hooks, keyword-only: ``_uniforms`` (fp32 [max_new_tokens, n_seq]) plants
+        the uniforms; ``_forced_tokens`` (int32 [n_seq, max_new_tokens]) feeds given tokens instead of the sampled ones
+        (teacher forcing).
+        Returns tokens[k][r] = the new token ids of sample r of prompt k, cut behind the first ``eos_token_id``; with
+        ``return_scores`` (test only) also the fp32 logits [steps, n_seq, vocab] every step sampled from."""
+        cfg, st = self.cfg, self.store
+        if self.lora is not None:
+            raise NotImplementedError("generate(): un-merged LoRA adapters are not supported - merge_lora() first")
+        if getattr(cfg, "arch", "llava") == "omnilmm" or self._row_splicer() is not None:
+            raise NotImplementedError("generate(): OmniLMM (resampler splice) is not supported")
+        if num_beams != 1:
+            raise NotImplementedError("generate(): beam search (num_beams > 1) is not supported")
+        if cfg.head_dim != 128:
+            raise NotImplementedError("generate(): rv_attn_decode needs head_dim 128")
+        if len(prompts) != len(images) or len(prompts) == 0:
+            raise ValueError(f"{len(prompts)} prompts for {len(images)} images")
+        if max_new_tokens < 1 or repeat < 1:
+            raise ValueError("generate(): max_new_tokens and repeat must be >= 1")
+        from .splice import plan_decode_rows
+        T, dev = int(max_new_tokens), self.device
+        was_training = self.training
+        self.eval()
+        try:
+            self._cur_drop_step = self._dropout_step
+            self._cur_drop = self._resolve_lora_drop()
+            cpu_plan = build_branch_plan([[p] for p in prompts], cfg.n_image_tokens, cfg.model_max_length,
+                                         splicer=None, pad_free=True, packed=False)
+            rows = plan_decode_rows(cpu_plan.row_off.tolist(), cpu_plan.row_len.tolist(), repeat, T)
+            M = rows.n_seq
+            self._rope(cpu_plan.L + T)
+            n_split = min(8, max(1, (cpu_plan.L + T) // 256))       # a function of the lengths only: the same bits at any repeat
+            caches = [torch.empty(rows.n_rows, 2 * cfg.kv_dim, dtype=BF16, device=dev) for _ in range(cfg.layers)]
+            logits = self._prefill(prompts, images, caches)[rows.prompt_of.long().to(dev)]       # [M, vocab_padded]
+            pre_off, pre_len, own_off = rows.pre_off.to(dev), rows.pre_len.to(dev), rows.own_off.to(dev)
+            rows = replace(rows, pre_len=pre_len, own_off=own_off)               # step() then computes on the device
+            sampling = temperature != 0.0
+            uniforms, forced_tokens = _uniforms, _forced_tokens
+            if sampling and uniforms is None:
+                uniforms = torch.rand(T, M, generator=generator, dtype=torch.float32)
+            if uniforms is not None:
+                if tuple(uniforms.shape) != (T, M):
+                    raise ValueError(f"generate(): _uniforms must be [{T}, {M}]")
+                uniforms = uniforms.to(dev, torch.float32).contiguous()
+            if forced_tokens is not None:
+                forced_tokens = torch.as_tensor(forced_tokens).to(dev, torch.int32).reshape(M, T)
+            seen = None
+            if repetition_penalty != 1.0:
+                seen_ids = torch.full((M, T), -1, dtype=torch.int32, device=dev)      # row m: its generated ids; -1 = none yet
+                seen = (torch.arange(M + 1, dtype=torch.int32, device=dev) * T, seen_ids.view(-1))
+            tokens = torch.zeros(M, T, dtype=torch.int32, device=dev)
+            done = torch.zeros(M, dtype=torch.bool, device=dev)
+            scores = []
+            n_steps = 0
+            for j in range(T):
+                if j > 0:
+                    logits = torch.empty(M, cfg.vocab_padded, dtype=torch.float32, device=dev)
+                    pos, dst, own_len = rows.step(j - 1)      # feeds token j - 1, generated last step
+                    for c0, c1 in rows.chunks:
+                        self._decode_step(tokens[c0:c1, j - 1].contiguous(), pos[c0:c1], dst[c0:c1],
+                                          (pre_off[c0:c1], pre_len[c0:c1], own_off[c0:c1], own_len[c0:c1]), caches, n_split,
+                                          logits[c0:c1])
+                tok, _ = ops.sample_token(logits, M, cfg.vocab, uniforms[j] if sampling else None, float(temperature),
+                                          float(top_p), seen=seen, penalty=float(repetition_penalty))
+                if forced_tokens is not None:
+                    tok = forced_tokens[:, j]
+                tokens[:, j] = tok
+                if seen is not None:
+                    seen_ids[:, j] = tok
+                if return_scores:
+                    scores.append(logits[:, :cfg.vocab].clone())
+                n_steps = j + 1
+                if eos_token_id is not None:
+                    done |= tok == int(eos_token_id)
+                    if j % 8 == 7 and bool(done.all()):            # the one read-back of the loop, every 8 steps
+                        break
+            host = tokens[:, :n_steps].cpu().tolist()
+            out = []
+            for k in range(len(prompts)):
+                out.append([])
+                for r in range(repeat):
+                    seq = host[k * repeat + r]
+                    if eos_token_id is not None and int(eos_token_id) in seq:
+                        seq = seq[:seq.index(int(eos_token_id)) + 1]
+                    out[-1].append(seq)
+            return (out, torch.stack(scores)) if return_scores else out
         finally:
             self.train(was_training)
 

@@ -751,6 +751,124 @@ def next_token_scores(logits: torch.Tensor, n_rows: int, v_valid: int, want_ids:
     return probs, logp, argmax, lse
 
 
+# ------------------------------------------------------------------------------------- KV-cached decode (csrc/decode.hip)
+def gemm_nt_skinny(a: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None,
+                   residual: Optional[torch.Tensor] = None, out_f32: bool = False) -> torch.Tensor:
+    """out[m][n] = sum_k a[m][k] w[n][k] (+ residual[m][n]) for 1 <= M <= 64 rows (rv_gemm_nt_skinny_bf16: the weight-streaming
+    products of a decode step).  ``out_f32``: fp32 output (the LM-head logits).  A row's result does not depend on M or on the
+    other rows."""
+    _chk2d(a, "a"), _chk2d(w, "w")
+    M, K = a.shape
+    N, Kw = w.shape
+    if K != Kw:
+        raise ValueError(f"gemm_nt_skinny: K mismatch {K} vs {Kw}")
+    if not 1 <= M <= 64:
+        raise ValueError(f"gemm_nt_skinny: 1 <= M <= 64 rows, got {M} (split the rows into chunks)")
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32 if out_f32 else BF16, device=a.device)
+    if out_f32:
+        if out.dim() != 2 or out.dtype != torch.float32 or out.stride(1) != 1 or out.device != a.device:
+            raise ValueError("gemm_nt_skinny: out must be a 2-D fp32 tensor with unit column stride on a's device")
+    else:
+        _chk2d(out, "out")
+    if tuple(out.shape) != (M, N):
+        raise ValueError(f"gemm_nt_skinny: out is {tuple(out.shape)}, expected {(M, N)}")
+    if residual is not None:
+        _chk2d(residual, "residual")
+        if tuple(residual.shape) != (M, N):
+            raise ValueError(f"gemm_nt_skinny: residual is {tuple(residual.shape)}, expected {(M, N)}")
+    hip.call("rv_gemm_nt_skinny_bf16", a, a.stride(0), w, w.stride(0), out, out.stride(0), M, N, K, residual,
+             residual.stride(0) if residual is not None else 0, int(out_f32))
+    return out
+
+
+_DECODE_WS = {}      # device -> fp32 workspace of attn_decode, grown on demand (stream-ordered reuse, like _splitk_ws)
+
+
+def attn_decode_workspace(device, M: int, H: int, n_split: int) -> torch.Tensor:
+    need = int(hip.lib().lib.rv_attn_decode_workspace_floats(M, H, n_split))
+    if need <= 0:
+        raise ValueError(f"attn_decode: bad (M, H, n_split) = {(M, H, n_split)}")
+    ws = _DECODE_WS.get(device)
+    if ws is None or ws.numel() < need:
+        ws = _DECODE_WS[device] = torch.empty(need, dtype=torch.float32, device=device)
+    return ws
+
+
+def attn_decode(q: torch.Tensor, kv: torch.Tensor, H: int, hd: int, k_col0: int, v_col0: int, spans, kv_group: int = 1,
+                n_split: int = 1, out: Optional[torch.Tensor] = None, want_lse: bool = False,
+                workspace: Optional[torch.Tensor] = None):
+    """Attention of one query token per sequence against a cache (rv_attn_decode).  ``q`` [M, >= H*hd] bf16 (head h at column
+    h*hd), ``kv`` [rows, ld] bf16 cache of one layer (K heads at k_col0, V heads at v_col0), ``spans`` = (pre_off, pre_len,
+    own_off, own_len) int32 [M]: sequence m attends cache rows [pre_off, pre_off + pre_len) then [own_off, own_off + own_len).
+    Returns (out [M, H*hd] bf16, lse [M, H] fp32 or None)."""
+    _chk2d(q, "q"), _chk2d(kv, "kv")
+    M = q.shape[0]
+    if q.shape[1] < H * hd:
+        raise ValueError(f"attn_decode: q has {q.shape[1]} columns, needs H * hd = {H * hd}")
+    if H % kv_group != 0:
+        raise ValueError("attn_decode: kv_group must divide H")
+    n_kv_cols = (H // kv_group) * hd
+    if not (0 <= k_col0 and k_col0 + n_kv_cols <= kv.shape[1] and 0 <= v_col0 and v_col0 + n_kv_cols <= kv.shape[1]):
+        raise ValueError(f"attn_decode: K / V head columns do not fit the cache's {kv.shape[1]} columns")
+    if len(spans) != 4:
+        raise ValueError("attn_decode: spans = (pre_off, pre_len, own_off, own_len)")
+    for name, t in zip(("pre_off", "pre_len", "own_off", "own_len"), spans):
+        if t.dtype != torch.int32 or t.numel() != M or not t.is_contiguous() or t.device != q.device:
+            raise ValueError(f"attn_decode: {name} must be contiguous int32 [{M}] on {q.device}")
+    if out is None:
+        out = torch.empty(M, H * hd, dtype=BF16, device=q.device)
+    _chk2d(out, "out")
+    if out.shape[0] != M or out.shape[1] < H * hd:
+        raise ValueError(f"attn_decode: out is {tuple(out.shape)}, needs [{M}, >= {H * hd}]")
+    if workspace is None:
+        workspace = attn_decode_workspace(q.device, M, H, n_split)
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != q.device:
+        raise ValueError("attn_decode: workspace must be a contiguous fp32 tensor on q's device")
+    lse = torch.empty(M, H, dtype=torch.float32, device=q.device) if want_lse else None
+    hip.call("rv_attn_decode", q, q.stride(0), kv, kv.stride(0), int(k_col0), int(v_col0), spans[0], spans[1], spans[2], spans[3],
+             out, out.stride(0), lse, M, H, hd, int(kv_group), 1.0 / math.sqrt(hd), int(n_split), workspace, workspace.numel())
+    return out, lse
+
+
+def sample_token(logits: torch.Tensor, n_rows: int, v_valid: int, u: Optional[torch.Tensor], temperature: float = 0.0,
+                 top_p: float = 1.0, seen: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, penalty: float = 1.0):
+    """One token per row of fp32 ``logits`` [rows, ld] over the columns [0, v_valid) (rv_sample_token): repetition penalty,
+    temperature, top-p, softmax, inverse-CDF draw from the caller's uniforms ``u`` (fp32 [n_rows] in [0, 1)); temperature 0 =
+    greedy (u may be None).  Returns (token int32 [n_rows], logp fp32 [n_rows])."""
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1 or not logits.is_cuda:
+        raise ValueError("sample_token: logits must be a 2-D fp32 CUDA tensor with unit column stride")
+    if not (0 < n_rows <= logits.shape[0] and 0 < v_valid <= logits.shape[1]):
+        raise ValueError(f"sample_token: {n_rows} rows x {v_valid} columns do not fit logits {tuple(logits.shape)}")
+    if not temperature >= 0.0:
+        raise ValueError("sample_token: temperature must be >= 0 (0 = greedy)")
+    if not top_p > 0.0:
+        raise ValueError("sample_token: top_p must be > 0")
+    if not penalty > 0.0:
+        raise ValueError("sample_token: the repetition penalty must be positive")
+    dev = logits.device
+    if u is None:
+        if temperature != 0.0:
+            raise ValueError("sample_token: sampling (temperature > 0) needs the uniforms u")
+    elif u.dtype != torch.float32 or u.numel() != n_rows or not u.is_contiguous() or u.device != dev:
+        raise ValueError(f"sample_token: u must be contiguous fp32 [{n_rows}] on the logits' device")
+    seen_off = seen_ids = None
+    if seen is not None and penalty != 1.0:
+        seen_off, seen_ids = seen
+        for name, t in (("seen_off", seen_off), ("seen_ids", seen_ids)):
+            if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"sample_token: {name} must be contiguous int32 on the logits' device")
+        if seen_off.numel() != n_rows + 1:
+            raise ValueError(f"sample_token: seen_off needs {n_rows + 1} entries")
+        if seen_ids.numel() == 0:
+            seen_off = seen_ids = None
+    token = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    logp = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    hip.call("rv_sample_token", logits, logits.stride(0), n_rows, v_valid, seen_off, seen_ids, float(penalty), float(temperature),
+             float(top_p), u, token, logp)
+    return token, logp
+
+
 def gemm_auto_variant(M: int, N: int) -> int:
     """The NT GEMM kernel the library picks for an [M, N] output when no variant is forced (gemm.hip dispatch: the 256 x 256
     tile kernel from 192 tiles on)."""

@@ -21,7 +21,7 @@ Two layouts:
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -533,3 +533,42 @@ def build_branch_plan(prompts: List[List[torch.Tensor]], n_img_tokens: int, mode
                       shared_len=shs if packed else None, n_real_tokens=int(sum(lens)), n_tokens=n_tokens,
                       row_off=torch.tensor(starts, dtype=torch.int32) if pad_free else None,
                       row_len=torch.tensor(lens, dtype=torch.int32) if pad_free else None, q_lo=q_lo, last_idx=last_idx)
+
+
+# ------------------------------------------------------------------------------------------------ KV-cached generation
+@dataclass
+class DecodeRows:
+    """Cache rows of ``LlavaDPOModel.generate``: every layer's cache is one [n_rows][2 kv_dim] buffer.  Rows [0, n_prefill) hold
+    the prompts exactly where the pad-free prefill put them; sequence m = prompt * repeat + sample then owns ``max_new`` rows of
+    its own behind them.  The samples of one prompt name the same prompt span (``pre_off`` / ``pre_len``): it is stored once."""
+    n_seq: int
+    n_rows: int                # rows of one layer's cache
+    prompt_of: torch.Tensor    # int32 [n_seq] the prompt (= prefill row) a sequence continues
+    pre_off: torch.Tensor      # int32 [n_seq] first cache row of its prompt
+    pre_len: torch.Tensor      # int32 [n_seq] tokens of the spliced prompt
+    own_off: torch.Tensor      # int32 [n_seq] first cache row of its generated tokens
+    chunks: List[Tuple[int, int]]   # [c0, c1) sequence ranges of at most ``max_rows`` rows: one launch set per chunk and step
+
+    def step(self, j: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Decode step j (it feeds generated token j, j = 0 the token sampled from the prefill): (RoPE position of that token,
+        the cache row its K | V go to, own_len INCLUDING it), int32 [n_seq] each."""
+        return self.pre_len + j, self.own_off + j, torch.full_like(self.pre_len, j + 1)
+
+
+def plan_decode_rows(row_off: Sequence[int], row_len: Sequence[int], repeat: int, max_new: int, max_rows: int = 64) -> DecodeRows:
+    """``row_off`` / ``row_len``: the pad-free prefill rows of the prompts (build_branch_plan(packed=False)), in prompt order."""
+    if repeat < 1 or max_new < 1 or max_rows < 1:
+        raise ValueError("plan_decode_rows: repeat, max_new and max_rows must be >= 1")
+    if len(row_off) != len(row_len) or len(row_off) == 0:
+        raise ValueError("plan_decode_rows: one (row_off, row_len) pair per prompt, at least one prompt")
+    off, ln = [int(x) for x in row_off], [int(x) for x in row_len]
+    if any(n < 1 for n in ln):
+        raise ValueError("plan_decode_rows: empty prompt")
+    n_prefill = max(o + n for o, n in zip(off, ln))
+    n_seq = len(off) * repeat
+    prompt_of = torch.arange(len(off), dtype=torch.int32).repeat_interleave(repeat)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32)                   # noqa: E731
+    return DecodeRows(n_seq=n_seq, n_rows=n_prefill + n_seq * max_new, prompt_of=prompt_of,
+                      pre_off=i32(off)[prompt_of.long()], pre_len=i32(ln)[prompt_of.long()],
+                      own_off=n_prefill + torch.arange(n_seq, dtype=torch.int32) * max_new,
+                      chunks=[(c, min(c + max_rows, n_seq)) for c in range(0, n_seq, max_rows)])
