@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import math
 import os
+from contextlib import contextmanager
 from dataclasses import dataclass, field, replace
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
@@ -153,10 +154,11 @@ def lora_group_rows(cfg: "LlavaConfig", grp: str) -> List[Tuple[int, int]]:
 LORA_SEED_SLOTS = {"qkv": (0, 4, 5), "o": (1,), "gu": (2, 6), "down": (3,)}
 
 
-class LoraDrop(NamedTuple):       # the adapter-dropout mode of ONE forward and of the backward that differentiates it
+class LoraDrop(NamedTuple):       # the pass state: the adapter-dropout mode of ONE forward and of the backward that differentiates it
     p: float = 0.0               # peft lora_dropout in effect; 0.0 = no dropout (full fine-tune, eval mode, lora_dropout = 0)
     per_module: bool = False     # one mask per peft module (RV_LORA_PEFT_MASKS) instead of one per fused projection
     fused: bool = False          # the kernels that produce a projection's input also write its dropped copy
+    step: int = 0                # the model's _dropout_step the pass ran at: seeds its masks (filled with or without dropout)
 
 
 class ProjSaved(NamedTuple):      # what an adapter projection keeps for its backward
@@ -393,7 +395,8 @@ class LlavaDPOModel:
         self.device = torch.device(device)
         self.lora = lora
         self.store = ParamStore(cfg, self.device, with_optimizer, lora)
-        self._dropout_step = 0          # advances once per forward: seeds the LoRA dropout masks
+        self._dropout_step = 0          # advances once per training forward: seeds the LoRA dropout masks
+        self._cur_drop = LoraDrop()     # the pass state of the forward / backward in flight (_begin_pass)
         # keep the dropped adapter inputs for backward (+1.3 GB per layer at 27 k tokens) instead of regenerating them
         self.keep_dropped_inputs = os.environ.get("RV_LORA_KEEP_DROPPED", "1") != "0"
         # keep normalised inputs and SwiGLU outputs for backward instead of recomputing them (RV_KEEP_RECOMPUTABLE=0:
@@ -641,26 +644,24 @@ class LlavaDPOModel:
             # through 23 layers are 84 % of the vision front's share - 27 % of the whole - of the per-token log-prob error variance
             # (profiles/r05_rounding_attribution.json), and the tower is 0.6 % of the step.  Every MFMA operand stays
             # bf16 (LayerNorm outputs, q / k / v, attention output, quick_gelu(fc1)); only out_proj / fc2 accumulate into an fp32 x.
-            x32 = ops.cast_bf16_to_f32(x)
-            for i in range(cfg.clip_layers_used):
-                h = ops.layernorm_fwd_f32in(x32, c[f"{i}.layer_norm1.w"], c[f"{i}.layer_norm1.b"], cfg.clip_eps)
-                qkv = ops.gemm_nt(h, c[f"{i}.wqkv"], bias=c[f"{i}.bqkv"])
-                a, _ = ops.attn_fwd(qkv, B, T, H, hd, False, 0, cd, 2 * cd)
-                ops.gemm_nt_f32res(a, c[f"{i}.wo"], c[f"{i}.bo"], x32)
-                h = ops.layernorm_fwd_f32in(x32, c[f"{i}.layer_norm2.w"], c[f"{i}.layer_norm2.b"], cfg.clip_eps)
-                h = ops.gemm_nt(h, c[f"{i}.fc1.w"], bias=c[f"{i}.fc1.b"], act=ops.ACT_QUICK_GELU)
-                ops.gemm_nt_f32res(h, c[f"{i}.fc2.w"], c[f"{i}.fc2.b"], x32)
-            x = ops.cast_f32_to_bf16(x32)            # hidden_states[-2] as the projector's bf16 GEMM operand: one rounding
-            idx = (torch.arange(B, device=self.device)[:, None] * T + 1 + torch.arange(P, device=self.device)[None]).reshape(-1)
-            return ops.gather_rows(x, idx.to(torch.int32))
+            x = ops.cast_bf16_to_f32(x)
+            norm = ops.layernorm_fwd_f32in
+            add_branch = ops.gemm_nt_f32res                     # x += a W^T + bias, in place
+        else:
+            norm = ops.layernorm_fwd
+
+            def add_branch(a, w, bias, x):
+                return ops.gemm_nt(a, w, bias=bias, residual=x)
         for i in range(cfg.clip_layers_used):
-            h = ops.layernorm_fwd(x, c[f"{i}.layer_norm1.w"], c[f"{i}.layer_norm1.b"], cfg.clip_eps)
+            h = norm(x, c[f"{i}.layer_norm1.w"], c[f"{i}.layer_norm1.b"], cfg.clip_eps)
             qkv = ops.gemm_nt(h, c[f"{i}.wqkv"], bias=c[f"{i}.bqkv"])
             a, _ = ops.attn_fwd(qkv, B, T, H, hd, False, 0, cd, 2 * cd)
-            x = ops.gemm_nt(a, c[f"{i}.wo"], bias=c[f"{i}.bo"], residual=x)
-            h = ops.layernorm_fwd(x, c[f"{i}.layer_norm2.w"], c[f"{i}.layer_norm2.b"], cfg.clip_eps)
+            x = add_branch(a, c[f"{i}.wo"], c[f"{i}.bo"], x)
+            h = norm(x, c[f"{i}.layer_norm2.w"], c[f"{i}.layer_norm2.b"], cfg.clip_eps)
             h = ops.gemm_nt(h, c[f"{i}.fc1.w"], bias=c[f"{i}.fc1.b"], act=ops.ACT_QUICK_GELU)
-            x = ops.gemm_nt(h, c[f"{i}.fc2.w"], bias=c[f"{i}.fc2.b"], residual=x)
+            x = add_branch(h, c[f"{i}.fc2.w"], c[f"{i}.fc2.b"], x)
+        if self.clip_fp32_resid:
+            x = ops.cast_f32_to_bf16(x)              # hidden_states[-2] as the projector's bf16 GEMM operand: one rounding
         idx = (torch.arange(B, device=self.device)[:, None] * T + 1 + torch.arange(P, device=self.device)[None]).reshape(-1)
         return ops.gather_rows(x, idx.to(torch.int32))
 
@@ -704,18 +705,33 @@ class LlavaDPOModel:
             return cfg.kv_dim, (cfg.hidden if cfg.kv_dim != cfg.hidden else 0)
         return (cfg.ffn, 0) if grp == "gu" else (0, 0)
 
-    def _resolve_lora_drop(self) -> LoraDrop:
-        """The adapter-dropout mode of the forward that starts now (peft lora_dropout: adapter models in training mode only).  It travels
-        in the forward's context: backward and a checkpointed layer's re-run follow it, whatever happened to the model in between."""
-        if self.lora is None or not self.training or not self.lora.lora_dropout > 0.0:
-            return LoraDrop()
-        fused = self.lora_fused_dropout and not self.lora_peft_masks
-        if fused and self.resid_fp32:
-            raise NotImplementedError("RV_RESID_FP32 with the producer-side LoRA dropout kernels (set RV_LORA_FUSED_DROPOUT=0)")
-        return LoraDrop(self.lora.lora_dropout, self.lora_peft_masks, fused)
+    def _begin_pass(self, advance: bool = False) -> LoraDrop:
+        """The state of the forward that starts now, stored as ``_cur_drop``: the dropout step (``advance``: of a new training step)
+        and the adapter-dropout mode (peft lora_dropout: adapter models in training mode only).  It travels in the forward's context:
+        backward and a checkpointed layer's re-run follow it, whatever happened to the model in between."""
+        if advance:
+            self._dropout_step += 1
+        drop = LoraDrop(step=self._dropout_step)
+        if self.lora is not None and self.training and self.lora.lora_dropout > 0.0:
+            fused = self.lora_fused_dropout and not self.lora_peft_masks
+            if fused and self.resid_fp32:
+                raise NotImplementedError("RV_RESID_FP32 with the producer-side LoRA dropout kernels (set RV_LORA_FUSED_DROPOUT=0)")
+            drop = drop._replace(p=self.lora.lora_dropout, per_module=self.lora_peft_masks, fused=fused)
+        self._cur_drop = drop
+        return drop
+
+    @contextmanager
+    def _eval_mode(self):
+        """Eval mode for a forward-only surface; the caller's mode comes back afterwards."""
+        was_training = self.training
+        self.eval()
+        try:
+            yield
+        finally:
+            self.train(was_training)
 
     def _dropout_seed(self, layer: int, slot: int) -> int:
-        return (self._cur_drop_step * 1000003 + self.dropout_rank * 7919 + layer * 8 + slot) & 0x7FFFFFFF
+        return (self._cur_drop.step * 1000003 + self.dropout_rank * 7919 + layer * 8 + slot) & 0x7FFFFFFF
 
     def _lora_mask(self, layer: int, grp: str) -> Tuple[float, int]:
         """(p, seed) of the mask a fused projection's adapter input shares; (0.0, 0) without dropout."""
@@ -858,20 +874,17 @@ class LlavaDPOModel:
         self._lora_wgrads(dy, dt, act, saved, i, "down")
         return dgu
 
-    def _layer_fwd(self, i: int, x: torch.Tensor, plan: SplicePlan, cos, sin, save: bool):
+    def _layer_fwd(self, i: int, x: torch.Tensor, pending: Optional[torch.Tensor], plan: SplicePlan, cos, sin, save: bool):
         """One decoder layer (HF LlamaDecoderLayer: RMSNorm, QKV, RoPE, causal attention, O + residual, RMSNorm, SwiGLU
-        + residual).  Returns (x_next, context for backward or None)."""
+        + residual).  ``pending``: on the fp32 stream (RV_RESID_FP32) the previous layer's bf16 down-projection branch, not yet
+        added to ``x``; None on the bf16 stream and in front of layer 0.  Returns (x_next, pending_next, context for backward or None)."""
         cfg, st = self.cfg, self.store
         d, H, hd = cfg.hidden, cfg.heads, cfg.head_dim
         S, L = plan.S, plan.L
         drop = self._cur_drop.fused   # this layer's norms and SwiGLU write the dropped copies their consumers' adapters read
         xnd = xn2d = actd = s_qkv = s_gu = None
-        pending = None
-        if isinstance(x, tuple):      # RV_RESID_FP32: (fp32 stream, the previous layer's bf16 down-projection branch not yet added to it)
-            x, pending = x
         if pending is not None:       # the add rides in this layer's first norm: x = stream + branch, xn = rmsnorm(x), one pass
             x, xn, rstd1 = ops.add_rmsnorm_fwd(x, pending, st.p(f"layers.{i}.ln1"), cfg.rms_eps)
-            del pending
         elif drop:
             xn, rstd1, xnd = ops.rmsnorm_fwd_dropout(x, st.p(f"layers.{i}.ln1"), cfg.rms_eps, *self._lora_mask(i, "qkv"))
         else:
@@ -906,21 +919,89 @@ class LlavaDPOModel:
                 act, actd = ops.swiglu_fwd_dropout(gu, *self._lora_mask(i, "down"))
             else:
                 act = ops.swiglu_fwd(gu)
-        if self.resid_fp32:
-            dwn, s_down = self._proj_fwd(act, i, "down", residual=None, xd=actd)
-            x_next = (x_mid, dwn)     # the NEXT layer's first norm (or the caller, after the last layer) adds the branch to the stream
+        if self.resid_fp32:           # the NEXT layer's first norm (or _run_stack, after the last layer) adds the branch to the stream
+            x_next = x_mid
+            branch, s_down = self._proj_fwd(act, i, "down", residual=None, xd=actd)
         else:
+            branch = None
             x_next, s_down = self._proj_fwd(act, i, "down", residual=x_mid, xd=actd)
         if not save:
-            return x_next, None
+            return x_next, branch, None
         keep = self.keep_recomputable
-        return x_next, dict(x=x, rstd1=rstd1, qkv=qkv, attn=attn, lse=lse, x_mid=x_mid, rstd2=rstd2, gu=gu,
-                            lora_qkv=s_qkv, lora_o=s_o, lora_gu=s_gu, lora_down=s_down,      # ProjSaved per projection (None: no adapters)
-                            # 288 GB of HBM: keep the cheap-to-recompute operands too (+1.05 GB / layer at 27 k tokens)
-                            # instead of re-running RMSNorm / SwiGLU in backward
-                            xn=xn if keep else None, xn2=xn2 if keep else None, act=act if keep else None)
+        lctx = dict(x=x, rstd1=rstd1, qkv=qkv, attn=attn, lse=lse, x_mid=x_mid, rstd2=rstd2, gu=gu,
+                    lora_qkv=s_qkv, lora_o=s_o, lora_gu=s_gu, lora_down=s_down,      # ProjSaved per projection (None: no adapters)
+                    # 288 GB of HBM: keep the cheap-to-recompute operands too (+1.05 GB / layer at 27 k tokens)
+                    # instead of re-running RMSNorm / SwiGLU in backward
+                    xn=xn if keep else None, xn2=xn2 if keep else None, act=act if keep else None)
+        return x_next, branch, lctx
+
+    def _run_stack(self, x: torch.Tensor, plan, save: bool = False, caches: Optional[List[torch.Tensor]] = None):
+        """The decoder stack over the spliced bf16 embeddings ``x`` [n_tokens, hidden] under the pass state of _begin_pass: every
+        surface's driver.  Returns (the final residual stream, the layers' backward contexts - empty unless ``save``).
+        ``save`` under --gradient_checkpointing keeps only each layer's INPUT (fp32 stream: with its pending branch added) and
+        backward runs the layer again.  ``caches``: per layer a [rows, 2 kv_dim] bf16 buffer whose first n_tokens rows receive the
+        layer's roped K | V columns."""
+        cfg = self.cfg
+        if self.resid_fp32:
+            x = ops.cast_bf16_to_f32(x)          # embedding / feature rows are bf16 values: exact
+        cos, sin = self._rope(plan.L)
+        keep = save and not self.gradient_checkpointing
+        pending, layers_ctx = None, []
+        for i in range(cfg.layers):
+            x_next, branch, lctx = self._layer_fwd(i, x, pending, plan, cos, sin, keep or caches is not None)
+            if caches is not None:
+                caches[i][:plan.n_tokens].copy_(lctx["qkv"][:, cfg.hidden:])      # device copy of the roped K | V columns (plumbing)
+            if keep:
+                layers_ctx.append(lctx)
+            elif save:
+                layers_ctx.append(dict(x=x if pending is None else ops.add_f32_bf16(x, pending), recompute=True))
+            del lctx
+            x, pending = x_next, branch
+        if pending is not None:
+            x = ops.add_f32_bf16(x, pending)     # the last layer's branch joins the fp32 stream
+        return x, layers_ctx
+
+    def _last_position_logits(self, plan: SplicePlan, images, caches: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
+        """Forward-only read-out behind every row's last token: embed + splice, the stack, the final norm at ``plan.last_idx`` and
+        the LM head in fp32.  Returns [round_up(n_seq, 64), vocab_padded] logits (rows >= n_seq are the LM head of zero rows)."""
+        cfg, st = self.cfg, self.store
+        self._begin_pass()
+        feats = self.encode_images(images)
+        x = ops.splice_fwd(plan.src, st.p("model.embed_tokens.weight"), feats, cfg.hidden)
+        x, _ = self._run_stack(x, plan, caches=caches)
+        n = plan.n_seq
+        hsel = torch.zeros(max(64, ops.round_up(n, 64)), cfg.hidden, dtype=BF16, device=self.device)
+        ops.rmsnorm_fwd(x, st.p("model.norm.weight"), cfg.rms_eps, row_idx=plan.last_idx, out=hsel[:n], want_rstd=False)
+        return ops.gemm_nt_f32(hsel, st.p("lm_head.weight"))
 
     # ------------------------------------------------------------------ forward
+    def _logps_plan(self, input_ids, labels, B: int, all_rows: bool, label_shift: int, token_weight, packed: bool):
+        """The plan of a forward_logps call, on the device, and the weights rv_seq_sum applies to its selected rows (or None)."""
+        cfg = self.cfg
+        args = (input_ids, labels, cfg.n_image_tokens, B, cfg.model_max_length)
+        if packed or (not all_rows and label_shift == 1 and self.share_prefix and input_ids.shape[0] == 2 * B):
+            plan = build_packed_plan(*args, cfg.pad_token_id, splicer=self._row_splicer(), pad_free=self.pad_free,
+                                     token_weight=token_weight, all_rows=packed)
+        else:
+            # label_shift != 1: the get_batch_logps_minicpm convention (labels pre-shifted, muffin_inference_logp.py:21-52),
+            # reference layout only
+            plan = build_splice_plan(*args, label_shift=1 if all_rows else label_shift, splicer=self._row_splicer(),
+                                     token_weight=token_weight)
+        w_rows = None
+        if all_rows and not packed:       # every position of the reference layout; masked ones take token id 0
+            nxt = plan.labels[:, 1:]
+            S_, Lm1 = nxt.shape
+            plan.sel_idx = (torch.arange(S_)[:, None] * plan.L + torch.arange(Lm1)[None]).reshape(-1).to(torch.int32)
+            plan.tgt = torch.where(nxt != -100, nxt, torch.zeros_like(nxt)).reshape(-1).to(torch.int32)
+            plan.seq_off = (torch.arange(S_ + 1) * Lm1).to(torch.int32)
+            plan.seq_of_row = torch.arange(S_).repeat_interleave(Lm1).to(torch.int32)
+            plan.n_sel = int(plan.sel_idx.numel())
+            w_rows = (nxt != -100).reshape(-1).to(torch.float32).to(self.device)     # loss_mask of get_batch_logps
+        plan = plan.to(self.device)
+        if token_weight is not None:
+            w_rows = plan.w_sel          # [n_sel] fp32: rv_seq_sum weighs the sums / counts, rv_row_coef the row coefficients
+        return plan, w_rows
+
     def forward_logps(self, input_ids: torch.Tensor, labels: torch.Tensor, images: torch.Tensor,
                       save_for_backward: bool = True, all_rows: bool = False, label_shift: int = 1,
                       token_weight: Optional[torch.Tensor] = None, packed: bool = False) -> StepOutput:
@@ -936,73 +1017,26 @@ class LlavaDPOModel:
         the packed TRAINING layout - the same plan, layer stack and launches as the training forward, so the values are the
         training step's bit for bit.  ``per_token_logp`` is the [2B, ld] matrix (row s owns its first ``plan.ev_len[s]``
         entries, the rest keep the fill 0), ``seq_logp`` / ``seq_cnt`` are rv_seq_sum over the compact vector of selected rows."""
-        if packed:
-            if not all_rows:
-                raise ValueError("packed=True is the all-positions precompute on the packed layout: pass all_rows=True")
+        B = len(images)                  # tensor [B, 3, H, W] or a list of raw uint8 [H, W, 3] images
+        if packed and not all_rows:
+            raise ValueError("packed=True is the all-positions precompute on the packed layout: pass all_rows=True")
+        if all_rows:
             if save_for_backward:
                 raise ValueError("all_rows is a forward-only mode")
-            if label_shift != 1:
+            if packed and label_shift != 1:
                 raise ValueError("packed=True needs the label_shift=1 convention (the packed layout has no MiniCPM variant)")
             if token_weight is not None:
                 raise ValueError("all_rows returns per-token log-probs; token weights apply to the selected-row step")
-            if input_ids.shape[0] != 2 * len(images):
+            if packed and input_ids.shape[0] != 2 * B:
                 raise ValueError("packed=True takes [2B, T] wins-then-rejects rows and B images")
         cfg, st = self.cfg, self.store
-        d, H, hd, f = cfg.hidden, cfg.heads, cfg.head_dim, cfg.ffn
-        B = len(images)                  # tensor [B, 3, H, W] or a list of raw uint8 [H, W, 3] images
-        ctx: dict = {}
-        w_rows = None
-        if self.training:            # evaluation passes between steps must not shift the dropout seeds of later steps
-            self._dropout_step += 1
-        self._cur_drop_step = ctx["dropout_step"] = self._dropout_step
-        self._cur_drop = ctx["lora_drop"] = self._resolve_lora_drop()
-        if packed:
-            plan = build_packed_plan(input_ids, labels, cfg.n_image_tokens, B, cfg.model_max_length, cfg.pad_token_id,
-                                     splicer=self._row_splicer(), pad_free=self.pad_free, all_rows=True)
-        elif all_rows:
-            if save_for_backward:
-                raise ValueError("all_rows is a forward-only mode")
-            if token_weight is not None:
-                raise ValueError("all_rows returns per-token log-probs; token weights apply to the selected-row step")
-            plan = build_splice_plan(input_ids, labels, cfg.n_image_tokens, B, cfg.model_max_length, splicer=self._row_splicer())
-            nxt = plan.labels[:, 1:]
-            S_, Lm1 = nxt.shape
-            plan.sel_idx = (torch.arange(S_)[:, None] * plan.L + torch.arange(Lm1)[None]).reshape(-1).to(torch.int32)
-            plan.tgt = torch.where(nxt != -100, nxt, torch.zeros_like(nxt)).reshape(-1).to(torch.int32)
-            plan.seq_off = (torch.arange(S_ + 1) * Lm1).to(torch.int32)
-            plan.seq_of_row = torch.arange(S_).repeat_interleave(Lm1).to(torch.int32)
-            plan.n_sel = int(plan.sel_idx.numel())
-            w_rows = (nxt != -100).reshape(-1).to(torch.float32).to(self.device)     # loss_mask of get_batch_logps
-        elif label_shift != 1:
-            # get_batch_logps_minicpm convention (labels pre-shifted, muffin_inference_logp.py:21-52): reference layout only
-            plan = build_splice_plan(input_ids, labels, cfg.n_image_tokens, B, cfg.model_max_length, label_shift=label_shift,
-                                     splicer=self._row_splicer(), token_weight=token_weight)
-        elif self.share_prefix and input_ids.shape[0] == 2 * B:
-            plan = build_packed_plan(input_ids, labels, cfg.n_image_tokens, B, cfg.model_max_length, cfg.pad_token_id,
-                                     splicer=self._row_splicer(), pad_free=self.pad_free, token_weight=token_weight)
-        else:
-            plan = build_splice_plan(input_ids, labels, cfg.n_image_tokens, B, cfg.model_max_length, splicer=self._row_splicer(),
-                                     token_weight=token_weight)
-        plan = plan.to(self.device)
-        if token_weight is not None:
-            w_rows = plan.w_sel          # [n_sel] fp32: rv_seq_sum weighs the sums / counts, rv_row_coef the row coefficients
-        S, L = plan.S, plan.L
-        N = plan.n_tokens                # S * L in the rectangular layouts, the sum of the packed rows' lengths when pad-free
+        d = cfg.hidden
+        # evaluation passes between steps must not shift the dropout seeds of later steps
+        ctx: dict = {"lora_drop": self._begin_pass(advance=self.training)}
+        plan, w_rows = self._logps_plan(input_ids, labels, B, all_rows, label_shift, token_weight, packed)
         feats = self.encode_images(images, ctx if save_for_backward else None)
         x = ops.splice_fwd(plan.src, st.p("model.embed_tokens.weight"), feats, d)
-        if self.resid_fp32:
-            x = ops.cast_bf16_to_f32(x)          # embedding / feature rows are bf16 values: exact
-        cos, sin = self._rope(L)
-        layers_ctx = []
-        for i in range(cfg.layers):
-            x_next, lctx = self._layer_fwd(i, x, plan, cos, sin, save_for_backward and not self.gradient_checkpointing)
-            if save_for_backward:
-                if lctx is None:      # --gradient_checkpointing: keep the layer's INPUT (fp32 stream: with its pending branch added)
-                    lctx = dict(x=x if not isinstance(x, tuple) else ops.add_f32_bf16(*x), recompute=True)
-                layers_ctx.append(lctx)
-            x = x_next
-        if isinstance(x, tuple):
-            x = ops.add_f32_bf16(*x)          # the last layer's branch joins the fp32 stream
+        x, layers_ctx = self._run_stack(x, plan, save=save_for_backward)
         if packed:
             return self._packed_all_rows_logps(x, plan)
         n_sel = plan.n_sel
@@ -1019,7 +1053,8 @@ class LlavaDPOModel:
         out = StepOutput(loss=None, scalars=None, per_pair=None, seq_logp=seq_logp, seq_cnt=seq_cnt,
                          per_token_logp=logp, plan=plan)
         if save_for_backward:
-            ctx.update(layers=layers_ctx, x_final=x, hsel=hsel, rstd_f=rstd_f, lse_v=lse_v, w_rows=w_rows, N=N, B=B)
+            # N: S * L in the rectangular layouts, the sum of the packed rows' lengths when pad-free
+            ctx.update(layers=layers_ctx, x_final=x, hsel=hsel, rstd_f=rstd_f, lse_v=lse_v, w_rows=w_rows, N=plan.n_tokens, B=B)
             out.ctx = ctx
         return out
 
@@ -1061,30 +1096,14 @@ class LlavaDPOModel:
         alone (omnilmm/model/omnilmm.py:371-396), i.e. from an empty id tensor with nothing to penalise.  Default 1.0 = off.
         Forward only, eval mode.  Returns (probs [n_q, K], logp [n_q, K], argmax int32 [n_q], lse [n_q]) on the
         device, questions in input order (image by image)."""
-        cfg, st = self.cfg, self.store
+        cfg = self.cfg
         if len(prompts) != len(images):
             raise ValueError(f"{len(prompts)} prompt lists for {len(images)} images")
-        was_training = self.training
-        self.eval()
-        try:
-            self._cur_drop_step = self._dropout_step
-            self._cur_drop = self._resolve_lora_drop()
+        with self._eval_mode():
             plan = build_branch_plan(prompts, cfg.n_image_tokens, cfg.model_max_length, splicer=self._row_splicer(),
                                      pad_free=self.pad_free or not packed, max_row_tokens=max_row_tokens, packed=packed)
-            plan = plan.to(self.device)
-            feats = self.encode_images(images)
-            x = ops.splice_fwd(plan.src, st.p("model.embed_tokens.weight"), feats, cfg.hidden)
-            if self.resid_fp32:
-                x = ops.cast_bf16_to_f32(x)
-            cos, sin = self._rope(plan.L)
-            for i in range(cfg.layers):
-                x, _ = self._layer_fwd(i, x, plan, cos, sin, False)
-            if isinstance(x, tuple):
-                x = ops.add_f32_bf16(*x)
+            logits = self._last_position_logits(plan.to(self.device), images)
             n_q = plan.n_seq
-            hsel = torch.zeros(max(64, ops.round_up(n_q, 64)), cfg.hidden, dtype=BF16, device=self.device)
-            ops.rmsnorm_fwd(x, st.p("model.norm.weight"), cfg.rms_eps, row_idx=plan.last_idx, out=hsel[:n_q], want_rstd=False)
-            logits = ops.gemm_nt_f32(hsel, st.p("lm_head.weight"))
             seen = None
             if repetition_penalty != 1.0:
                 uniq = [torch.unique(ids.cpu().long()) for plist in prompts for ids in plist]
@@ -1094,36 +1113,15 @@ class LlavaDPOModel:
                 seen = (off.to(self.device), torch.cat(uniq).to(torch.int32).to(self.device))
             want = torch.as_tensor(want_ids, dtype=torch.int32).reshape(-1).to(self.device)
             return ops.next_token_scores(logits, n_q, cfg.vocab, want, seen=seen, penalty=float(repetition_penalty))
-        finally:
-            self.train(was_training)
 
     # ------------------------------------------------------------------ KV-cached candidate generation
     def _prefill(self, prompts, images, caches: Optional[List[torch.Tensor]] = None):
-        """One plain causal pad-free row per prompt through the existing forward (encode_images, splice, _layer_fwd: today's
-        bits).  Returns fp32 last-position logits [round_up(n, 64), vocab_padded] (rows >= n are the LM head of zero rows).
+        """One plain causal pad-free row per prompt through the training forward's stack (_last_position_logits: its bits).  Returns fp32 last-position logits [round_up(n, 64), vocab_padded] (rows >= n are the LM head of zero rows).
         ``caches``: per layer a [rows, 2 kv_dim] bf16 buffer; the layer's roped K | V rows are copied to its first n_tokens rows."""
-        cfg, st = self.cfg, self.store
-        d = cfg.hidden
-        self._cur_drop_step = self._dropout_step
-        self._cur_drop = self._resolve_lora_drop()
+        cfg = self.cfg
         plan = build_branch_plan([[p] for p in prompts], cfg.n_image_tokens, cfg.model_max_length, splicer=self._row_splicer(),
                                  pad_free=True, packed=False).to(self.device)
-        feats = self.encode_images(images)
-        x = ops.splice_fwd(plan.src, st.p("model.embed_tokens.weight"), feats, d)
-        if self.resid_fp32:
-            x = ops.cast_bf16_to_f32(x)
-        cos, sin = self._rope(plan.L)
-        for i in range(cfg.layers):
-            x, lctx = self._layer_fwd(i, x, plan, cos, sin, caches is not None)
-            if caches is not None:
-                caches[i][:plan.n_tokens].copy_(lctx["qkv"][:, d:])      # device copy of the roped K | V columns (plumbing)
-                del lctx
-        if isinstance(x, tuple):
-            x = ops.add_f32_bf16(*x)
-        n = plan.n_seq
-        hsel = torch.zeros(max(64, ops.round_up(n, 64)), d, dtype=BF16, device=self.device)
-        ops.rmsnorm_fwd(x, st.p("model.norm.weight"), cfg.rms_eps, row_idx=plan.last_idx, out=hsel[:n], want_rstd=False)
-        return ops.gemm_nt_f32(hsel, st.p("lm_head.weight"))
+        return self._last_position_logits(plan, images, caches)
 
     def _decode_step(self, tok: torch.Tensor, pos: torch.Tensor, dst: torch.Tensor, spans, caches: List[torch.Tensor],
                      n_split: int, out: torch.Tensor):
@@ -1169,7 +1167,7 @@ class LlavaDPOModel:
         """The sampling branch of the AI-feedback stage (muffin/llava15_gen_data.py:335-357: ``generate(do_sample=True,
         temperature=, max_new_tokens=, use_cache=True)`` on a dataset that repeats every item ``--repeat`` times): ``repeat``
         candidate answers per (image, prompt) with a KV cache.  ``prompts[k]``: 1-D input_ids with the image placeholder,
-        about ``images[k]``.  Prefill = the existing forward, one pad-free causal row per prompt, whose roped K | V rows become
+        about ``images[k]``.  Prefill (_prefill) = the training forward's stack, one pad-free causal row per prompt, whose roped K | V rows become
         the first rows of every layer's cache - stored ONCE per prompt, the ``repeat`` samples attend the same rows
         (splice.plan_decode_rows).  Each decode step runs len(prompts) * repeat sequences (chunks of <= 64 rows) through
         norm, rv_gemm_nt_skinny_bf16, RoPE, scatter into the cache, rv_attn_decode, SwiGLU and rv_sample_token; the loop is a
@@ -1201,11 +1199,7 @@ class LlavaDPOModel:
             raise ValueError("generate(): max_new_tokens and repeat must be >= 1")
         from .splice import plan_decode_rows
         T, dev = int(max_new_tokens), self.device
-        was_training = self.training
-        self.eval()
-        try:
-            self._cur_drop_step = self._dropout_step
-            self._cur_drop = self._resolve_lora_drop()
+        with self._eval_mode():
             cpu_plan = build_branch_plan([[p] for p in prompts], cfg.n_image_tokens, cfg.model_max_length,
                                          splicer=None, pad_free=True, packed=False)
             rows = plan_decode_rows(cpu_plan.row_off.tolist(), cpu_plan.row_len.tolist(), repeat, T)
@@ -1266,8 +1260,6 @@ class LlavaDPOModel:
                         seq = seq[:seq.index(int(eos_token_id)) + 1]
                     out[-1].append(seq)
             return (out, torch.stack(scores)) if return_scores else out
-        finally:
-            self.train(was_training)
 
     # ------------------------------------------------------------------ backward
     def backward(self, out: StepOutput, coef: torch.Tensor):
@@ -1280,7 +1272,7 @@ class LlavaDPOModel:
         hook = self.grad_ready_hook
 
         lora = self.lora is not None
-        self._cur_drop_step, self._cur_drop = ctx.get("dropout_step", 0), ctx.get("lora_drop", LoraDrop())
+        self._cur_drop = ctx.get("lora_drop", LoraDrop())      # the pass state of the forward being differentiated
         scratch_dw = torch.empty(d, dtype=BF16, device=self.device) if lora else None   # gains are frozen under LoRA
 
         def wgrad(dy: torch.Tensor, xin: torch.Tensor, key: str):
@@ -1313,7 +1305,7 @@ class LlavaDPOModel:
         for i in reversed(range(cfg.layers)):
             c = ctx["layers"][i]
             if c.get("recompute"):      # --gradient_checkpointing: only the layer input was kept; run the layer again
-                _, c = self._layer_fwd(i, c["x"], plan, cos, sin, True)
+                _, _, c = self._layer_fwd(i, c["x"], None, plan, cos, sin, True)
             act = c["act"] if c["act"] is not None else ops.swiglu_fwd(c["gu"], interleaved=st.interleave_gu)
             c["act"] = None
             if st.interleave_gu and self.lora is None:
@@ -1386,15 +1378,8 @@ class LlavaDPOModel:
         if S * L * cfg.vocab * 2 > (16 << 30):
             raise ValueError("forward(): logits would exceed 16 GB - use forward_logps (fused LM head) for training shapes")
         x = inputs_embeds.to(self.device, BF16).reshape(S * L, d).contiguous()
-        if self.resid_fp32:
-            x = ops.cast_bf16_to_f32(x)
-        plan = SimpleNamespace(S=S, L=L, pos=None, seg=None, rows=None, branches=None)
-        cos, sin = self._rope(L)
-        self._cur_drop = self._resolve_lora_drop()
-        for i in range(cfg.layers):
-            x, _ = self._layer_fwd(i, x, plan, cos, sin, False)
-        if isinstance(x, tuple):
-            x = ops.add_f32_bf16(*x)
+        self._begin_pass()
+        x, _ = self._run_stack(x, SimpleNamespace(S=S, L=L, pos=None, seg=None, rows=None, branches=None))
         h, _ = ops.rmsnorm_fwd(x, st.p("model.norm.weight"), cfg.rms_eps, want_rstd=False)
         logits = ops.gemm_nt(h, st.p("lm_head.weight"))[:, :cfg.vocab]          # drop the vocabulary padding columns
         return SimpleNamespace(logits=logits.reshape(S, L, cfg.vocab), loss=None)
