@@ -98,6 +98,22 @@ __device__ __forceinline__ f32x4_t ds_read_f32x4_asm(uint32_t lds_addr, int imm_
   return v;
 }
 
+// ---- The dropout mask (rv_dropout and every kernel that regenerates its mask): a counter hash of (seed-derived key, element
+// index in the contiguous tensor the mask is defined on).  One 32-bit word serves the element pair (2 q, 2 q + 1): an element is
+// kept iff its 16 bits (low half: the even element) are >= thresh16, and kept values are scaled by inv_keep.
+__device__ __forceinline__ uint32_t drop_mix32(uint32_t h) {
+  h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
+  return h;
+}
+// keep bits of element pair q (= element index / 2): drop_pair_bits(low 32 bits of q, drop_base(the bits of q above them, key))
+__device__ __forceinline__ uint32_t drop_base(uint32_t q_hi, uint32_t key) { return q_hi * 0x9e3779b9u + key; }
+__device__ __forceinline__ uint32_t drop_pair_bits(uint32_t q_lo, uint32_t base) { return drop_mix32(q_lo ^ base); }
+// the keep decision for the two elements of a pair with keep bits h
+__device__ __forceinline__ void drop_keep2(uint32_t h, uint32_t thresh16, float inv_keep, float& even, float& odd) {
+  even = ((h & 0xffffu) >= thresh16) ? even * inv_keep : 0.f;
+  odd = ((h >> 16) >= thresh16) ? odd * inv_keep : 0.f;
+}
+
 // f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N-1>{}): a loop whose index is a template constant
 // (hard-register asm helpers are selected by it)
 template <int N, class F>
@@ -106,6 +122,13 @@ __device__ __forceinline__ void static_for(F&& f) {
     static_for<N - 1>(f);
     f(std::integral_constant<int, N - 1>{});
   }
+}
+
+// The dropout parameters every kernel argument list carries, derived on the host in this one place: an element is kept iff its
+// 16 hash bits are >= thresh16 = round(p * 65536); key seeds the hash; kept values are scaled by inv_keep = 1 / (1 - p).
+struct DropParams { uint32_t thresh16, key; float inv_keep; };
+inline DropParams drop_params(float p, int seed) {
+  return DropParams{(uint32_t)((double)p * 65536.0 + 0.5), (uint32_t)seed * 0x9e3779b9u + 0x85ebca6bu, 1.f / (1.f - p)};
 }
 
 // Error plumbing for the C ABI (no exceptions across the boundary).

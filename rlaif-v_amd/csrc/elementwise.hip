@@ -20,22 +20,14 @@ __device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
   return v;
 }
 
-__device__ __forceinline__ uint32_t mix32(uint32_t h) {
-  h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
-  return h;
-}
 // rv_dropout applied to one 16-byte chunk (8 bf16 values, chunk index i8 in the CONTIGUOUS tensor the mask is defined on): the
 // arithmetic of dropout_kernel, so a producer kernel can emit the dropped copy of its output bit-identically
 __device__ __forceinline__ uint4 dropout_chunk(const uint4 v, long i8, uint32_t thresh16, float inv_keep, uint32_t key) {
   float f[8];
   unpack8(v, f);
-  const uint32_t base = (uint32_t)(i8 >> 30) * 0x9e3779b9u + key;
+  const uint32_t base = drop_base((uint32_t)(i8 >> 30), key);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t h = mix32(((uint32_t)i8 * 4u + (uint32_t)j) ^ base);
-    f[2 * j] = ((h & 0xffffu) >= thresh16) ? f[2 * j] * inv_keep : 0.f;
-    f[2 * j + 1] = ((h >> 16) >= thresh16) ? f[2 * j + 1] * inv_keep : 0.f;
-  }
+  for (int j = 0; j < 4; ++j) drop_keep2(drop_pair_bits((uint32_t)i8 * 4u + (uint32_t)j, base), thresh16, inv_keep, f[2 * j], f[2 * j + 1]);
   return pack8(f);
 }
 
@@ -527,13 +519,9 @@ __global__ void dropout_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict_
     unpack8(((const uint4*)x)[i], f);
     // one 32-bit hash serves two elements (16 random bits each: p is resolved to 1.5e-5) - the integer multiplies
     // of the mixer, not HBM, bound this kernel otherwise
-    const uint32_t base = (uint32_t)(i >> 30) * 0x9e3779b9u + key;
+    const uint32_t base = drop_base((uint32_t)(i >> 30), key);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const uint32_t h = mix32(((uint32_t)i * 4u + (uint32_t)j) ^ base);
-      f[2 * j] = ((h & 0xffffu) >= thresh16) ? f[2 * j] * inv_keep : 0.f;
-      f[2 * j + 1] = ((h >> 16) >= thresh16) ? f[2 * j + 1] * inv_keep : 0.f;
-    }
+    for (int j = 0; j < 4; ++j) drop_keep2(drop_pair_bits((uint32_t)i * 4u + (uint32_t)j, base), thresh16, inv_keep, f[2 * j], f[2 * j + 1]);
     if (y) ((uint4*)y)[i] = pack8(f);
     if (acc) {
       float a[8];
@@ -1175,9 +1163,9 @@ int rv_rmsnorm_fwd_dropout(const void* x, long ldx, const int* row_idx, const vo
   RV_REQUIRE(d % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "rv_rmsnorm_fwd_dropout: d/ld must be multiples of 8");
   RV_REQUIRE(yd != nullptr && p >= 0.f && p < 1.f, "rv_rmsnorm_fwd_dropout: yd required, 0 <= p < 1");
   if (rows == 0) return 0;
+  const DropParams dp = drop_params(p, seed);
   hipLaunchKernelGGL(rmsnorm_fwd_kernel<true>, dim3(min(rows, 8192)), dim3(256), 0, STREAM(stream), (const bf16_t*)x, ldx,
-                     row_idx, (const bf16_t*)w, (bf16_t*)y, ldy, rstd, rows, d, eps, (bf16_t*)yd,
-                     (uint32_t)((double)p * 65536.0 + 0.5), 1.f / (1.f - p), (uint32_t)seed * 0x9e3779b9u + 0x85ebca6bu);
+                     row_idx, (const bf16_t*)w, (bf16_t*)y, ldy, rstd, rows, d, eps, (bf16_t*)yd, dp.thresh16, dp.inv_keep, dp.key);
   RV_CHECK_LAUNCH();
   return 0;
 }
@@ -1333,9 +1321,9 @@ int rv_swiglu_fwd_dropout(const void* gu, long ldgu, void* act, long lda, long r
   RV_REQUIRE(f % 8 == 0 && ldgu % 8 == 0 && lda % 8 == 0, "rv_swiglu_fwd_dropout: alignment");
   RV_REQUIRE(actd != nullptr && p >= 0.f && p < 1.f, "rv_swiglu_fwd_dropout: actd required, 0 <= p < 1");
   if (rows == 0) return 0;
+  const DropParams dp = drop_params(p, seed);
   hipLaunchKernelGGL((swiglu_fwd_kernel<0, true>), dim3(grid_for(rows * (f / 8), 256, 16384)), dim3(256), 0, STREAM(stream),
-                     (const bf16_t*)gu, ldgu, (bf16_t*)act, lda, rows, f, (bf16_t*)actd, (uint32_t)((double)p * 65536.0 + 0.5),
-                     1.f / (1.f - p), (uint32_t)seed * 0x9e3779b9u + 0x85ebca6bu);
+                     (const bf16_t*)gu, ldgu, (bf16_t*)act, lda, rows, f, (bf16_t*)actd, dp.thresh16, dp.inv_keep, dp.key);
   RV_CHECK_LAUNCH();
   return 0;
 }
@@ -1376,9 +1364,9 @@ int rv_dropout(const void* x, void* y, void* acc, long n, float p, int seed, voi
   RV_REQUIRE(p >= 0.f && p < 1.f, "rv_dropout: 0 <= p < 1");
   RV_REQUIRE(y != nullptr || acc != nullptr, "rv_dropout: need an output (y) or an accumulator (acc)");
   if (n == 0) return 0;
-  const uint32_t thresh = (uint32_t)((double)p * 65536.0 + 0.5);        // 16 random bits per element
+  const DropParams dp = drop_params(p, seed);                           // 16 random bits per element
   hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0, STREAM(stream), (const bf16_t*)x,
-                     (bf16_t*)y, (bf16_t*)acc, n / 8, thresh, 1.f / (1.f - p), (uint32_t)seed * 0x9e3779b9u + 0x85ebca6bu);
+                     (bf16_t*)y, (bf16_t*)acc, n / 8, dp.thresh16, dp.inv_keep, dp.key);
   RV_CHECK_LAUNCH();
   return 0;
 }

@@ -2,8 +2,11 @@
 #include "gemm.hpp"
 #include "rlaifv_hip.h"
 
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include <initializer_list>
 
 static thread_local char g_err[512] = "";
 void rv_set_error(const char* msg) {
@@ -11,39 +14,167 @@ void rv_set_error(const char* msg) {
   g_err[sizeof(g_err) - 1] = 0;
 }
 
+// ---- A/B knobs: each is read through one accessor, from the first call of any entry point on ----
+static int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 // variants: 0 = 128x128x64 register staging, 1 = 128x128x64 global_load_lds, 2 = 256x256x32 ping-pong,
 // -1 (default) = pick 2 when the problem fills the chip with 256x256 tiles, else 1.
 static int g_default_variant = -1;
-static int g_group = 0;     // experiment knob: RV_GEMM_GROUP
+// RV_EPI_WIDE=0: the 4-wide EpiStore path
 static int epi_narrow() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("RV_EPI_WIDE"); v = (e && atoi(e) == 0) ? 1 : 0; }
+  static const int v = env_int("RV_EPI_WIDE", 1) == 0 ? 1 : 0;
   return v;
 }
-static void read_group_env() {
-  static bool env_done = false;
-  if (!env_done) { const char* e = getenv("RV_GEMM_GROUP"); if (e) g_group = atoi(e); env_done = true; }
+// experiment knob RV_GEMM_GROUP: row tiles per scheduling group (GemmShape::group)
+static int gemm_group() {
+  static const int v = env_int("RV_GEMM_GROUP", 0);
+  return v;
+}
+// RV_GEMM_MI16 (default 1): the 16x16x32-MFMA main loops of the 64-deep-A NN kernel and the TN kernel (gemm.hpp "MI16"); 0 = 32x32x16
+static int g_mi16 = -1;
+static int nn_mi16() {
+  if (g_mi16 < 0) g_mi16 = env_int("RV_GEMM_MI16", 1);
+  return g_mi16;
 }
 
-template <class Epi, bool DMA_IN_MSEG>
-static int launch_gemm256(const GemmShape& g, const Epi& epi, hipStream_t st) {
-  constexpr int LDS = 4 * G2_STAGE_BYTES;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_nt_256_kernel<Epi, DMA_IN_MSEG>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_done = true;
+// ---- the one launch helper: raises the kernel's dynamic-LDS limit the first time THIS instantiation is launched (once per
+// process, as before), launches, and reports a failure of either step as rc 2 ----
+template <auto Kernel, class... Args>
+static int launch(int lds, dim3 grid, dim3 block, hipStream_t st, const Args&... args) {
+  static bool limit_raised = false;
+  if (lds > 0 && !limit_raised) {
+    const hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();                  // or the next launch's RV_CHECK_LAUNCH would report this one
+      snprintf(g_err, sizeof(g_err), "raising a kernel's dynamic-LDS limit to %d bytes: %s", lds, hipGetErrorString(e));
+      return 2;
+    }
+    limit_raised = true;
   }
-  const int tiles_m = (g.M + G2_BM - 1) / G2_BM, tiles_n = (g.N + G2_BN - 1) / G2_BN;
-  hipLaunchKernelGGL((gemm_nt_256_kernel<Epi, DMA_IN_MSEG>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), LDS, st, g, epi);
+  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
   RV_CHECK_LAUNCH();
   return 0;
 }
 
-// RV_GEMM_MI16 (default 1): the 16x16x32-MFMA main loops of the 64-deep-A NN kernel and the TN kernel (gemm.hpp "MI16"); 0 = 32x32x16
-static int g_mi16 = -1;
-static int nn_mi16() {
-  if (g_mi16 < 0) { const char* e = getenv("RV_GEMM_MI16"); g_mi16 = e ? atoi(e) : 1; }
-  return g_mi16;
+static int tiles(int n, int tile) { return (n + tile - 1) / tile; }
+// the chip-fill rule of the 256x256 kernels (ops.py _fills_chip mirrors it)
+static bool fills_chip(const GemmShape& g) { return (long)tiles(g.M, G2_BM) * tiles(g.N, G2_BN) >= 192; }
+
+// ---- argument checks.  Every message names the entry point that was called. ----
+static int reject(const char* who, const char* what) {
+  snprintf(g_err, sizeof(g_err), "%s: %s", who, what);
+  return 1;
+}
+#define REQ(cond, what)                         \
+  do {                                          \
+    if (!(cond)) return reject(who, what);      \
+  } while (0)
+#define CHECK(call)                             \
+  do {                                          \
+    if (call) return 1;                         \
+  } while (0)
+
+// leading dimensions, in elements: multiples of 8 where rows are moved 16 bytes at a time (every input, and the bf16 outputs of
+// the rope and SwiGLU epilogues), multiples of 4 for the other outputs and the residuals
+static int check_ld(const char* who, std::initializer_list<long> by8, std::initializer_list<long> by4) {
+  for (long ld : by8) REQ(ld % 8 == 0, "a leading dimension of rows moved 16 bytes at a time must be a multiple of 8 elements");
+  for (long ld : by4) REQ(ld % 4 == 0, "the leading dimension of an output or a residual must be a multiple of 4 elements");
+  return 0;
+}
+static int check_align(const char* who, std::initializer_list<const void*> ptrs, int bytes, const char* names) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= (uintptr_t)p;
+  if (bits & (uintptr_t)(bytes - 1)) {
+    snprintf(g_err, sizeof(g_err), "%s: %s must be %d-byte aligned", who, names, bytes);
+    return 1;
+  }
+  return 0;
+}
+// column groups of the second contraction segment: whole N tiles (128 for the NT kernels, 256 for the NN ones) that tile N
+static int check_groups(const char* who, int group_cols, int group0, int N, int tile) {
+  if (group_cols == 0 || (group_cols % tile == 0 && group0 % tile == 0 && group0 >= 0 && group0 <= N &&
+                          (N - (group0 ? group0 : group_cols)) % group_cols == 0))
+    return 0;
+  snprintf(g_err, sizeof(g_err), "%s: group_cols / group0 must be multiples of %d that tile N (group0 + k * group_cols = N)", who, tile);
+  return 1;
+}
+static int check_p(const char* who, float p) {
+  REQ(p >= 0.f && p < 1.f, "0 <= p < 1");
+  return 0;
+}
+// what the NT kernels ask of (A, B, N, K)
+static int check_shape(const GemmShape& g, const char* who) {
+  REQ(g.K % GEMM_BK == 0 && g.K > 0, "K must be a positive multiple of 64");
+  REQ(g.N % 4 == 0, "N must be a multiple of 4");
+  CHECK(check_ld(who, {g.lda, g.ldb}, {}));
+  return check_align(who, {g.A, g.B}, 16, "A/B");
+}
+
+static GemmShape shape(const void* A, long lda, const void* B, long ldb, int M, int N, int K) {
+  return GemmShape{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, gemm_group()};
+}
+static GemmShape shape_ext(const void* A, long lda, const void* B, long ldb, int M, int N, int K, const void* A2, long lda2,
+                           const void* B2, long ldb2, int K2, int group_cols, int group0) {
+  return GemmShape{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, gemm_group(),
+                   (const bf16_t*)A2, (const bf16_t*)B2, lda2, ldb2, K2, group_cols, group0};
+}
+static EpiStore epi_store(void* C, long ldc, const void* bias, const void* residual, long ldr, int act, float alpha) {
+  EpiStore epi{(bf16_t*)C, ldc, (const bf16_t*)bias, (const bf16_t*)residual, ldr, act, alpha};
+  epi.narrow = epi_narrow();
+  return epi;
+}
+
+// ---- NT launchers: 128x128 tiles (STAGE 0 = register staging, 1 = LDS-DMA) and 256x256 ping-pong; EXT = second K segment ----
+template <int STAGE, class Epi, bool EXT = false>
+static int launch_gemm(const GemmShape& g, const Epi& epi, hipStream_t st) {
+  return launch<gemm_nt_kernel<STAGE, Epi, EXT>>(GEMM_LDS_BYTES, dim3(tiles(g.M, GEMM_BM) * tiles(g.N, GEMM_BN)), dim3(GEMM_THREADS),
+                                                 st, g, epi);
+}
+template <class Epi, bool DMA_IN_MSEG, bool EXT = false>
+static int launch_gemm256(const GemmShape& g, const Epi& epi, hipStream_t st) {
+  return launch<gemm_nt_256_kernel<Epi, DMA_IN_MSEG, EXT>>(4 * G2_STAGE_BYTES, dim3(tiles(g.M, G2_BM) * tiles(g.N, G2_BN)),
+                                                           dim3(G2_THREADS), st, g, epi);
+}
+
+template <class Epi>
+static int dispatch(const char* who, const GemmShape& g, const Epi& epi, int variant, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (variant < 0) variant = g_default_variant;
+  if (variant < 0) variant = fills_chip(g) ? 3 : 1;
+  REQ(variant <= 3, "GEMM variant: 0..3");
+  if (variant == 3) return launch_gemm256<Epi, true>(g, epi, st);
+  if (variant == 2) return launch_gemm256<Epi, false>(g, epi, st);
+  if (variant == 1) return launch_gemm<1, Epi>(g, epi, st);
+  return launch_gemm<0, Epi>(g, epi, st);
+}
+
+// GEMMs with a second contraction segment (GemmShape::A2/B2/K2): the 256x256 ping-pong kernel when the problem
+// fills the chip and the column groups are tile aligned, else the 128x128 kernel.
+template <class Epi>
+static int dispatch_ext(const GemmShape& g, const Epi& epi, void* stream) {
+  if (fills_chip(g) && g.group_cols % G2_BN == 0 && g.group0 % G2_BN == 0)
+    return launch_gemm256<Epi, true, true>(g, epi, (hipStream_t)stream);
+  return launch_gemm<1, Epi, true>(g, epi, (hipStream_t)stream);
+}
+
+// ---- the NN launcher: the 64-deep-A kernel when K allows (K % 64 == 0, K >= 512; with EXT also K2 % 64 == 0), with the
+// 16x16x32 main loop unless RV_GEMM_MI16=0, else the 32-deep kernel.  A64_ONLY: the entry point has required such a K, and the
+// 32-deep kernel is not instantiated for its epilogue.  PRE (adapter segment first) exists in the 64-deep kernel only.
+// (Any order of the three launches is correct.  This one - 32-deep, 64-deep, 64-deep MI16 - is the order the functions have had
+// in .text, and the bytes of the TN kernels depend on where they lie: reordering shows up as four changed digests in
+// kernel_resources.py --digest, see that tool's docstring.) ----
+template <class Epi, bool EXT = false, bool PRE = false, bool A64_ONLY = PRE>
+static int launch_nn(const GemmShape& g, const Epi& epi, hipStream_t st) {
+  static_assert(A64_ONLY || !PRE, "the adapter-first form has no 32-deep kernel");
+  const dim3 grid(tiles(g.M, G2_BM) * tiles(g.N, G2_BN)), block(G2_THREADS);
+  [[maybe_unused]] const bool a64 = A64_ONLY || (g.K % 64 == 0 && g.K >= 512 && (!EXT || g.K2 % 64 == 0));
+  if constexpr (!A64_ONLY) {
+    if (!a64) return launch<gemm_nn_256_kernel<Epi, EXT>>(G2_LDS_BYTES, grid, block, st, g, epi);
+  }
+  if (!nn_mi16()) return launch<gemm_nn_a64_kernel<Epi, EXT, false, PRE>>(G4_LDS_BYTES, grid, block, st, g, epi);
+  return launch<gemm_nn_a64_kernel<Epi, EXT, true, PRE>>(G4_LDS_BYTES, grid, block, st, g, epi);
 }
 
 // TN kernel: prefetch distance 3 (128 KiB LDS ring; distance 4 measured equal)
@@ -52,23 +183,20 @@ static int launch_gemm_tn(const bf16_t* P, long ldp, const bf16_t* Q, long ldq, 
                           hipStream_t st, int splits = 1, int r_chunk = 0, long split_stride = 0, int bid0 = 0,
                           int nblocks = 0) {
   constexpr int DIST = 3, LDS = (DIST + 1) * G2_STAGE_BYTES;
-  read_group_env();
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_tn_256_kernel<Epi, DIST>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_tn_256_kernel<Epi, DIST, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_done = true;
-  }
-  const int tiles_i = (I + 255) / 256, tiles_j = (J + 255) / 256;
-  const int gx = nblocks > 0 ? nblocks : tiles_i * tiles_j;          // launch-order positions bid0 .. bid0 + gx - 1
-  if (nn_mi16())
-    hipLaunchKernelGGL((gemm_tn_256_kernel<Epi, DIST, true>), dim3(gx, splits), dim3(G2_THREADS), LDS, st, P,
-                       ldp, Q, ldq, R, I, J, epi, r_chunk, split_stride, g_group, bid0);
-  else
-    hipLaunchKernelGGL((gemm_tn_256_kernel<Epi, DIST>), dim3(gx, splits), dim3(G2_THREADS), LDS, st, P,
-                       ldp, Q, ldq, R, I, J, epi, r_chunk, split_stride, g_group, bid0);
-  RV_CHECK_LAUNCH();
-  return 0;
+  const int gx = nblocks > 0 ? nblocks : tiles(I, 256) * tiles(J, 256);          // launch-order positions bid0 .. bid0 + gx - 1
+  const dim3 grid(gx, splits), block(G2_THREADS);
+  if (!nn_mi16())
+    return launch<gemm_tn_256_kernel<Epi, DIST>>(LDS, grid, block, st, P, ldp, Q, ldq, R, I, J, epi, r_chunk, split_stride, gemm_group(),
+                                                 bid0);
+  return launch<gemm_tn_256_kernel<Epi, DIST, true>>(LDS, grid, block, st, P, ldp, Q, ldq, R, I, J, epi, r_chunk, split_stride,
+                                                     gemm_group(), bid0);
+}
+
+// Token-axis split of a TN product: `splits` chunks of r_chunk rows (a multiple of 32), none of them empty
+struct SplitK { int splits, r_chunk; };
+static SplitK splitk_chunks(int R, int splits) {
+  const int r_chunk = ((R + splits - 1) / splits + 31) / 32 * 32;
+  return SplitK{(R + r_chunk - 1) / r_chunk, r_chunk};
 }
 
 // Tail split of a weight-gradient GEMM.  All output tiles cost the same (the contraction runs over every token), so a
@@ -98,9 +226,9 @@ static TnTailPlan tn_tail_plan(int R, int I, int J) {
   if (1.0 - best < 0.15) return p;                             // not worth two more launches
   p.full_blocks = full * 256;
   p.tail = tail;
-  p.splits = best_s;
-  p.r_chunk = ((R + best_s - 1) / best_s + 31) / 32 * 32;
-  p.splits = (R + p.r_chunk - 1) / p.r_chunk;
+  const SplitK s = splitk_chunks(R, best_s);
+  p.splits = s.splits;
+  p.r_chunk = s.r_chunk;
   return p;
 }
 
@@ -125,52 +253,6 @@ __global__ __launch_bounds__(256) void tn_tail_reduce_kernel(const float* __rest
   }
 }
 
-template <int STAGE, class Epi>
-static int launch_gemm(const GemmShape& g, const Epi& epi, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_nt_kernel<STAGE, Epi>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        GEMM_LDS_BYTES);
-    attr_done = true;
-  }
-  const int tiles_m = (g.M + GEMM_BM - 1) / GEMM_BM, tiles_n = (g.N + GEMM_BN - 1) / GEMM_BN;
-  hipLaunchKernelGGL((gemm_nt_kernel<STAGE, Epi>), dim3(tiles_m * tiles_n), dim3(GEMM_THREADS), GEMM_LDS_BYTES, st, g,
-                     epi);
-  RV_CHECK_LAUNCH();
-  return 0;
-}
-
-// GEMMs with a second contraction segment (GemmShape::A2/B2/K2): the 256x256 ping-pong kernel when the problem
-// fills the chip and the column groups are tile aligned, else the 128x128 kernel.
-template <class Epi>
-static int dispatch_ext(const GemmShape& g, const Epi& epi, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const long t256 = (long)((g.M + G2_BM - 1) / G2_BM) * ((g.N + G2_BN - 1) / G2_BN);
-  if (t256 >= 192 && g.group_cols % G2_BN == 0 && g.group0 % G2_BN == 0) {
-    constexpr int LDS = 4 * G2_STAGE_BYTES;
-    static bool attr_done = false;
-    if (!attr_done) {
-      hipFuncSetAttribute((const void*)gemm_nt_256_kernel<Epi, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      attr_done = true;
-    }
-    hipLaunchKernelGGL((gemm_nt_256_kernel<Epi, true, true>),
-                       dim3(((g.M + G2_BM - 1) / G2_BM) * ((g.N + G2_BN - 1) / G2_BN)), dim3(G2_THREADS), LDS, st, g, epi);
-    RV_CHECK_LAUNCH();
-    return 0;
-  }
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_nt_kernel<1, Epi, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                        GEMM_LDS_BYTES);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((gemm_nt_kernel<1, Epi, true>),
-                     dim3(((g.M + GEMM_BM - 1) / GEMM_BM) * ((g.N + GEMM_BN - 1) / GEMM_BN)), dim3(GEMM_THREADS),
-                     GEMM_LDS_BYTES, st, g, epi);
-  RV_CHECK_LAUNCH();
-  return 0;
-}
-
 // out[i][j] = bf16(alpha * sum_s ws[s][i][j])   (deterministic second pass of the split-K TN GEMM)
 __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int splits, int I, int J, float alpha,
                                      bf16_t* __restrict__ out, long ldc) {
@@ -189,93 +271,32 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int splits, i
     *(uint2*)(out + i * ldc + j) = o;
   }
 }
-
-template <class Epi>
-static int dispatch(const GemmShape& g, const Epi& epi, int variant, void* stream) {
-  read_group_env();
-  if (variant < 0) variant = g_default_variant;
-  if (variant < 0) {
-    const long t256 = (long)((g.M + G2_BM - 1) / G2_BM) * ((g.N + G2_BN - 1) / G2_BN);
-    variant = (t256 >= 192) ? 3 : 1;
-  }
-  if (variant > 3) { rv_set_error("GEMM variant: 0..3"); return 1; }
-  if (variant == 3) return launch_gemm256<Epi, true>(g, epi, (hipStream_t)stream);
-  if (variant == 2) return launch_gemm256<Epi, false>(g, epi, (hipStream_t)stream);
-  if (variant == 1) return launch_gemm<1, Epi>(g, epi, (hipStream_t)stream);
-  return launch_gemm<0, Epi>(g, epi, (hipStream_t)stream);
-}
-
-static int check_shape(const GemmShape& g, const char* who) {
-  if (g.K % GEMM_BK != 0 || g.K <= 0) { rv_set_error("GEMM: K must be a positive multiple of 64"); return 1; }
-  if (g.N % 4 != 0) { rv_set_error("GEMM: N must be a multiple of 4"); return 1; }
-  if (g.lda % 8 != 0 || g.ldb % 8 != 0) { rv_set_error("GEMM: lda/ldb must be multiples of 8 elements"); return 1; }
-  if (((uintptr_t)g.A | (uintptr_t)g.B) & 15) { rv_set_error("GEMM: A/B must be 16-byte aligned"); return 1; }
-  (void)who;
-  return 0;
-}
-
-// NN GEMM with one of the SwiGLU epilogues: the 64-deep-A kernel when K allows, else the 32-deep one
-template <class Epi>
-static int launch_nn_epi(const GemmShape& g, const Epi& epi, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_nn_256_kernel<Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES);
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<Epi, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    attr_done = true;
-  }
-  const int tiles_m = (g.M + G2_BM - 1) / G2_BM, tiles_n = (g.N + G2_BN - 1) / G2_BN;
-  if (g.K % 64 == 0 && g.K >= 512 && nn_mi16())
-    hipLaunchKernelGGL((gemm_nn_a64_kernel<Epi, false, true>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES, st, g, epi);
-  else if (g.K % 64 == 0 && g.K >= 512)
-    hipLaunchKernelGGL((gemm_nn_a64_kernel<Epi>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES, st, g, epi);
-  else
-    hipLaunchKernelGGL((gemm_nn_256_kernel<Epi>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G2_LDS_BYTES, st, g, epi);
-  RV_CHECK_LAUNCH();
-  return 0;
+static int launch_splitk_reduce(const float* ws, int splits, int I, int J, float alpha, void* out, long ldc, hipStream_t st) {
+  const long blocks = ((long)I * J / 4 + 255) / 256;
+  return launch<splitk_reduce_kernel>(0, dim3((int)(blocks < 2048 ? blocks : 2048)), dim3(256), st, ws, splits, I, J, alpha, (bf16_t*)out,
+                                      ldc);
 }
 
 // ---- LoRA adapter dropout with one mask per peft module (kernels: gemm.hpp "ONE MASK PER peft MODULE") ----
 static LoraMasks lora_masks(float p, int seed0, int seed1, int seed2) {
+  const DropParams d = drop_params(p, seed0);                 // threshold and 1 / (1 - p) are the same for every module
   LoraMasks dm;
-  const int seeds[3] = {seed0, seed1, seed2};
-  for (int g = 0; g < 3; ++g) dm.key[g] = (uint32_t)seeds[g] * 0x9e3779b9u + 0x85ebca6bu;
-  dm.thresh16 = (uint32_t)((double)p * 65536.0 + 0.5);
-  dm.inv_keep = 1.f / (1.f - p);
+  dm.thresh16 = d.thresh16;
+  dm.inv_keep = d.inv_keep;
+  dm.key[0] = d.key;
+  dm.key[1] = drop_params(p, seed1).key;
+  dm.key[2] = drop_params(p, seed2).key;
   return dm;
 }
 
-template <int G, int NST>
-static int launch_lora_masks_fwd(const bf16_t* X, long ldx, const bf16_t* A, long lda, bf16_t* T, long ldt, int M, int K, float alpha,
-                                 const LoraMasks& dm, hipStream_t st) {
-  constexpr int LDS = NST * (16384 + G * 8192);
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)lora_masks_fwd_kernel<G, NST, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)lora_masks_fwd_kernel<G, NST, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_done = true;
+// f(std::integral_constant<int, G>{}) for the G = FIRST .. 3 modules of a fused projection
+template <int FIRST = 1, class F>
+static int for_modules(int G, F&& f) {
+  if constexpr (FIRST <= 1) {
+    if (G == 1) return f(std::integral_constant<int, 1>{});
   }
-  const dim3 grid((M + 127) / 128), block(256);
-  if (dm.thresh16) hipLaunchKernelGGL((lora_masks_fwd_kernel<G, NST, true>), grid, block, LDS, st, X, ldx, A, lda, T, ldt, M, K, alpha, dm);
-  else hipLaunchKernelGGL((lora_masks_fwd_kernel<G, NST, false>), grid, block, LDS, st, X, ldx, A, lda, T, ldt, M, K, alpha, dm);
-  RV_CHECK_LAUNCH();
-  return 0;
-}
-
-template <int G>
-static int launch_lora_masks_dgrad(const bf16_t* dT, long lddt, const bf16_t* AT, long ldat, bf16_t* C, long ldc, const bf16_t* R,
-                                   long ldr, int M, int N, const LoraMasks& dm, hipStream_t st) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)lora_masks_dgrad_kernel<G, true>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-    hipFuncSetAttribute((const void*)lora_masks_dgrad_kernel<G, false>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_LDS_BYTES);
-    attr_done = true;
-  }
-  const dim3 grid(((M + GEMM_BM - 1) / GEMM_BM) * ((N + GEMM_BN - 1) / GEMM_BN)), block(GEMM_THREADS);
-  if (dm.thresh16) hipLaunchKernelGGL((lora_masks_dgrad_kernel<G, true>), grid, block, GEMM_LDS_BYTES, st, dT, lddt, AT, ldat, C, ldc, R, ldr, M, N, dm);
-  else hipLaunchKernelGGL((lora_masks_dgrad_kernel<G, false>), grid, block, GEMM_LDS_BYTES, st, dT, lddt, AT, ldat, C, ldc, R, ldr, M, N, dm);
-  RV_CHECK_LAUNCH();
-  return 0;
+  if (G == 2) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 3>{});
 }
 
 extern "C" {
@@ -298,39 +319,35 @@ int rv_set_gemm_mi16(int on) {
 int rv_gemm_nt_bf16(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
                     const void* bias, const void* residual, long ldr, int act, float alpha, int variant,
                     void* stream) {
+  const char* const who = __func__;
   if (M == 0 || N == 0) return 0;
-  GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group};
-  if (check_shape(g, "rv_gemm_nt_bf16")) return 1;
-  RV_REQUIRE(ldc % 4 == 0 && (residual == nullptr || ldr % 4 == 0), "rv_gemm_nt_bf16: ldc/ldr must be multiples of 4");
+  const GemmShape g = shape(A, lda, B, ldb, M, N, K);
+  CHECK(check_shape(g, who));
+  CHECK(check_ld(who, {}, {ldc, residual ? ldr : 0}));
   // many rows, at most 256 columns, plain store: the streaming kernel (the rank-r side of LoRA)
   if (variant < 0 && g_default_variant < 0 && N % GSK_BN == 0 && N <= 256 && M >= 4096 && bias == nullptr &&
-      residual == nullptr && act == RV_ACT_NONE && ((uintptr_t)C & 7) == 0) {
-    static bool attr_done = false;
-    if (!attr_done) {
-      hipFuncSetAttribute((const void*)gemm_nt_skinny_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GSK_LDS_BYTES);
-      attr_done = true;
-    }
-    hipLaunchKernelGGL(gemm_nt_skinny_kernel, dim3(((M + GSK_BM - 1) / GSK_BM) * (N / GSK_BN)), dim3(256), GSK_LDS_BYTES,
-                       (hipStream_t)stream, g, (bf16_t*)C, ldc, alpha);
-    RV_CHECK_LAUNCH();
-    return 0;
-  }
-  EpiStore epi{(bf16_t*)C, ldc, (const bf16_t*)bias, (const bf16_t*)residual, ldr, act, alpha};
-  epi.narrow = epi_narrow();
-  return dispatch(g, epi, variant, stream);
+      residual == nullptr && act == RV_ACT_NONE && ((uintptr_t)C & 7) == 0)
+    return launch<gemm_nt_skinny_kernel>(GSK_LDS_BYTES, dim3(tiles(M, GSK_BM) * (N / GSK_BN)), dim3(256), (hipStream_t)stream, g,
+                                         (bf16_t*)C, ldc, alpha);
+  return dispatch(who, g, epi_store(C, ldc, bias, residual, ldr, act, alpha), variant, stream);
+}
+
+// what the TN entries share: R > 0, an [I, J] output of whole 8-element pieces
+static int check_tn(const char* who, int R, int I, int J) {
+  REQ(R > 0, "R must be > 0");
+  REQ(I % 8 == 0 && J % 8 == 0 && I >= 8 && J >= 8, "I and J must be multiples of 8");
+  return 0;
 }
 
 int rv_gemm_tn_bf16(const void* P, long ldp, const void* Q, long ldq, void* C, long ldc, int R, int I, int J,
                     const void* residual, long ldr, float alpha, void* stream) {
+  const char* const who = __func__;
   if (I == 0 || J == 0) return 0;
-  RV_REQUIRE(R > 0, "rv_gemm_tn_bf16: R must be > 0");
-  RV_REQUIRE(I % 8 == 0 && J % 8 == 0 && I >= 8 && J >= 8, "rv_gemm_tn_bf16: I and J must be multiples of 8");
-  RV_REQUIRE(ldp % 8 == 0 && ldq % 8 == 0 && ldc % 4 == 0 && (residual == nullptr || ldr % 4 == 0),
-             "rv_gemm_tn_bf16: leading dimensions must be multiples of 8 (inputs) / 4 (output)");
-  RV_REQUIRE((((uintptr_t)P | (uintptr_t)Q) & 15) == 0, "rv_gemm_tn_bf16: P/Q must be 16-byte aligned");
-  EpiStore epi{(bf16_t*)C, ldc, nullptr, (const bf16_t*)residual, ldr, RV_ACT_NONE, alpha};
-  epi.narrow = epi_narrow();
-  return launch_gemm_tn((const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, R, I, J, epi, (hipStream_t)stream);
+  CHECK(check_tn(who, R, I, J));
+  CHECK(check_ld(who, {ldp, ldq}, {ldc, residual ? ldr : 0}));
+  CHECK(check_align(who, {P, Q}, 16, "P/Q"));
+  return launch_gemm_tn((const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, R, I, J, epi_store(C, ldc, nullptr, residual, ldr, RV_ACT_NONE, alpha),
+                        (hipStream_t)stream);
 }
 
 int rv_gemm_tn_workspace_floats(int R, int I, int J) {
@@ -341,191 +358,117 @@ int rv_gemm_tn_workspace_floats(int R, int I, int J) {
 
 int rv_gemm_tn_bf16_ws(const void* P, long ldp, const void* Q, long ldq, void* C, long ldc, int R, int I, int J,
                        float* workspace, long workspace_floats, void* stream) {
+  const char* const who = __func__;
   if (I == 0 || J == 0) return 0;
-  RV_REQUIRE(R > 0, "rv_gemm_tn_bf16_ws: R must be > 0");
-  RV_REQUIRE(I % 8 == 0 && J % 8 == 0 && I >= 8 && J >= 8, "rv_gemm_tn_bf16_ws: I and J must be multiples of 8");
-  RV_REQUIRE(ldp % 8 == 0 && ldq % 8 == 0 && ldc % 4 == 0, "rv_gemm_tn_bf16_ws: leading dimensions must be multiples of 8 (inputs) / 4 (output)");
-  RV_REQUIRE((((uintptr_t)P | (uintptr_t)Q | (uintptr_t)workspace) & 15) == 0, "rv_gemm_tn_bf16_ws: P/Q/workspace must be 16-byte aligned");
-  RV_REQUIRE(((uintptr_t)C & 7) == 0, "rv_gemm_tn_bf16_ws: C must be 8-byte aligned (the tail reduce stores 4 bf16 at a time)");
+  CHECK(check_tn(who, R, I, J));
+  CHECK(check_ld(who, {ldp, ldq}, {ldc}));
+  CHECK(check_align(who, {P, Q, workspace}, 16, "P/Q/workspace"));
+  CHECK(check_align(who, {C}, 8, "C (the tail reduce stores 4 bf16 at a time)"));
+  const bf16_t *p_ = (const bf16_t*)P, *q_ = (const bf16_t*)Q;
+  hipStream_t st = (hipStream_t)stream;
   const TnTailPlan p = tn_tail_plan(R, I, J);
-  EpiStore epi{(bf16_t*)C, ldc, nullptr, nullptr, 0, RV_ACT_NONE, 1.0f};
-  epi.narrow = epi_narrow();
+  const EpiStore epi = epi_store(C, ldc, nullptr, nullptr, 0, RV_ACT_NONE, 1.0f);
   if (p.splits <= 1 || workspace == nullptr || workspace_floats < (long)p.splits * p.tail * 65536)
-    return launch_gemm_tn((const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, R, I, J, epi, (hipStream_t)stream);
-  if (launch_gemm_tn((const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, R, I, J, epi, (hipStream_t)stream, 1, 0, 0, 0, p.full_blocks))
-    return 1;
-  EpiStoreF32 epf{workspace, 256};
-  if (launch_gemm_tn((const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, R, I, J, epf, (hipStream_t)stream, p.splits, p.r_chunk, -1,
-                     p.full_blocks, p.tail))
-    return 1;
-  read_group_env();
-  hipLaunchKernelGGL(tn_tail_reduce_kernel, dim3(p.tail), dim3(256), 0, (hipStream_t)stream, workspace, p.splits, p.tail,
-                     p.full_blocks, I, J, g_group, (bf16_t*)C, ldc);
-  RV_CHECK_LAUNCH();
-  return 0;
+    return launch_gemm_tn(p_, ldp, q_, ldq, R, I, J, epi, st);
+  if (launch_gemm_tn(p_, ldp, q_, ldq, R, I, J, epi, st, 1, 0, 0, 0, p.full_blocks)) return 1;
+  if (launch_gemm_tn(p_, ldp, q_, ldq, R, I, J, EpiStoreF32{workspace, 256}, st, p.splits, p.r_chunk, -1, p.full_blocks, p.tail)) return 1;
+  return launch<tn_tail_reduce_kernel>(0, dim3(p.tail), dim3(256), st, (const float*)workspace, p.splits, p.tail, p.full_blocks, I, J,
+                                       gemm_group(), (bf16_t*)C, ldc);
 }
 
 int rv_gemm_nt_lora_bf16(const void* A, long lda, const void* B, long ldb, const void* A2, long lda2, const void* B2,
                          long ldb2, int K2, int group_cols, int group0, void* C, long ldc, int M, int N, int K,
                          const void* residual, long ldr, void* stream) {
+  const char* const who = __func__;
   if (M == 0 || N == 0) return 0;
-  GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group,
-              (const bf16_t*)A2, (const bf16_t*)B2, lda2, ldb2, K2, group_cols, group0};
-  if (check_shape(g, "rv_gemm_nt_lora_bf16")) return 1;
-  RV_REQUIRE(K2 > 0 && K2 % GEMM_BK == 0, "rv_gemm_nt_lora_bf16: K2 must be a positive multiple of 64");
-  RV_REQUIRE(lda2 % 8 == 0 && ldb2 % 8 == 0 && ((((uintptr_t)A2 | (uintptr_t)B2) & 15) == 0),
-             "rv_gemm_nt_lora_bf16: A2/B2 must be 16-byte aligned with leading dimensions multiples of 8");
-  RV_REQUIRE(group_cols == 0 || (group_cols % GEMM_BN == 0 && group0 % GEMM_BN == 0 && group0 >= 0 && group0 <= N &&
-                                 (N - (group0 ? group0 : group_cols)) % group_cols == 0),
-             "rv_gemm_nt_lora_bf16: group_cols / group0 must be multiples of 128 that tile N (group0 + k * group_cols = N)");
-  RV_REQUIRE(ldc % 4 == 0 && (residual == nullptr || ldr % 4 == 0), "rv_gemm_nt_lora_bf16: ldc/ldr must be multiples of 4");
-  EpiStore epi{(bf16_t*)C, ldc, nullptr, (const bf16_t*)residual, ldr, RV_ACT_NONE, 1.0f};
-  epi.narrow = epi_narrow();
-  return dispatch_ext(g, epi, stream);
+  const GemmShape g = shape_ext(A, lda, B, ldb, M, N, K, A2, lda2, B2, ldb2, K2, group_cols, group0);
+  CHECK(check_shape(g, who));
+  REQ(K2 > 0 && K2 % GEMM_BK == 0, "K2 must be a positive multiple of 64");
+  CHECK(check_ld(who, {lda2, ldb2}, {ldc, residual ? ldr : 0}));
+  CHECK(check_align(who, {A2, B2}, 16, "A2/B2"));
+  CHECK(check_groups(who, group_cols, group0, N, GEMM_BN));
+  return dispatch_ext(g, epi_store(C, ldc, nullptr, residual, ldr, RV_ACT_NONE, 1.0f), stream);
 }
 
-static int nn_bias_act(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K, const void* bias,
-                       const void* residual, long ldr, int act, float alpha, void* stream);
+// rv_gemm_nn_bf16 and rv_gemm_nn_bias_act_bf16
+static int nn_bias_act(const char* who, const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
+                       const void* bias, const void* residual, long ldr, int act, float alpha, void* stream) {
+  if (M == 0 || N == 0) return 0;
+  REQ(K > 0 && K % G2_BK == 0, "K must be a positive multiple of 32");
+  REQ(N % 8 == 0 && N >= 8, "N must be a multiple of 8");
+  CHECK(check_ld(who, {lda, ldb}, {ldc, residual ? ldr : 0}));
+  CHECK(check_align(who, {A, B}, 16, "A/B"));
+  return launch_nn(shape(A, lda, B, ldb, M, N, K), epi_store(C, ldc, bias, residual, ldr, act, alpha), (hipStream_t)stream);
+}
 
 int rv_gemm_nn_bf16(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
                     const void* residual, long ldr, float alpha, void* stream) {
-  return nn_bias_act(A, lda, B, ldb, C, ldc, M, N, K, nullptr, residual, ldr, RV_ACT_NONE, alpha, stream);
+  return nn_bias_act(__func__, A, lda, B, ldb, C, ldc, M, N, K, nullptr, residual, ldr, RV_ACT_NONE, alpha, stream);
 }
 
 int rv_gemm_nn_bias_act_bf16(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
                              const void* bias, const void* residual, long ldr, int act, float alpha, void* stream) {
-  RV_REQUIRE(act == RV_ACT_NONE || act == RV_ACT_QUICK_GELU || act == RV_ACT_GELU, "rv_gemm_nn_bias_act_bf16: unknown activation");
-  RV_REQUIRE(bias == nullptr || ((uintptr_t)bias & 15) == 0, "rv_gemm_nn_bias_act_bf16: bias must be 16-byte aligned");
-  return nn_bias_act(A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, act, alpha, stream);
-}
-
-static int nn_bias_act(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K, const void* bias,
-                       const void* residual, long ldr, int act, float alpha, void* stream) {
-  if (M == 0 || N == 0) return 0;
-  RV_REQUIRE(K > 0 && K % G2_BK == 0, "rv_gemm_nn_bf16: K must be a positive multiple of 32");
-  RV_REQUIRE(N % 8 == 0 && N >= 8, "rv_gemm_nn_bf16: N must be a multiple of 8");
-  RV_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0 && (residual == nullptr || ldr % 4 == 0),
-             "rv_gemm_nn_bf16: leading dimensions must be multiples of 8 (inputs) / 4 (output)");
-  RV_REQUIRE((((uintptr_t)A | (uintptr_t)B) & 15) == 0, "rv_gemm_nn_bf16: A/B must be 16-byte aligned");
-  read_group_env();
-  GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group};
-  EpiStore epi{(bf16_t*)C, ldc, (const bf16_t*)bias, (const bf16_t*)residual, ldr, act, alpha};
-  epi.narrow = epi_narrow();
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_nn_256_kernel<EpiStore>, hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES);
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiStore>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiStore, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    attr_done = true;
-  }
-  const int tiles_m = (M + G2_BM - 1) / G2_BM, tiles_n = (N + G2_BN - 1) / G2_BN;
-  if (K % 64 == 0 && K >= 512 && nn_mi16())
-    hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiStore, false, true>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
-                       (hipStream_t)stream, g, epi);
-  else if (K % 64 == 0 && K >= 512)
-    hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiStore>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
-                       (hipStream_t)stream, g, epi);
-  else
-    hipLaunchKernelGGL((gemm_nn_256_kernel<EpiStore>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G2_LDS_BYTES,
-                       (hipStream_t)stream, g, epi);
-  RV_CHECK_LAUNCH();
-  return 0;
+  const char* const who = __func__;
+  REQ(act == RV_ACT_NONE || act == RV_ACT_QUICK_GELU || act == RV_ACT_GELU, "unknown activation");
+  CHECK(check_align(who, {bias}, 16, "bias"));
+  return nn_bias_act(who, A, lda, B, ldb, C, ldc, M, N, K, bias, residual, ldr, act, alpha, stream);
 }
 
 int rv_gemm_nn_rope_bf16(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
                          const float* cos_tab, const float* sin_tab, const int* pos, int L, int rope_cols, int hd, void* stream) {
+  const char* const who = __func__;
   if (M == 0 || N == 0) return 0;
-  RV_REQUIRE(hd == 128, "rv_gemm_nn_rope_bf16: head dim 128 only");
-  RV_REQUIRE(K >= 512 && K % 64 == 0, "rv_gemm_nn_rope_bf16: K must be a multiple of 64 and >= 512 (64-deep-A kernel)");
-  RV_REQUIRE(N % 256 == 0 && rope_cols % 256 == 0 && rope_cols >= 0 && rope_cols <= N,
-             "rv_gemm_nn_rope_bf16: N and rope_cols must be multiples of 256 (a 256-column tile holds q / k heads or v heads)");
-  RV_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0, "rv_gemm_nn_rope_bf16: leading dimensions must be multiples of 8");
-  RV_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)cos_tab | (uintptr_t)sin_tab) & 15) == 0,
-             "rv_gemm_nn_rope_bf16: operands and tables must be 16-byte aligned");
-  RV_REQUIRE(cos_tab && sin_tab && L > 0, "rv_gemm_nn_rope_bf16: tables / L");
-  read_group_env();
-  GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group};
-  EpiStoreRope epi{(bf16_t*)C, ldc, cos_tab, sin_tab, pos, L, rope_cols};
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiStoreRope>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiStoreRope, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    attr_done = true;
-  }
-  const int tiles_m = (M + G2_BM - 1) / G2_BM, tiles_n = (N + G2_BN - 1) / G2_BN;
-  if (nn_mi16())
-    hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiStoreRope, false, true>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
-                       (hipStream_t)stream, g, epi);
-  else
-    hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiStoreRope>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
-                       (hipStream_t)stream, g, epi);
-  RV_CHECK_LAUNCH();
-  return 0;
+  REQ(hd == 128, "hd must be 128");
+  REQ(K >= 512 && K % 64 == 0, "K must be a multiple of 64 and >= 512 (64-deep-A kernel)");
+  REQ(N % 256 == 0 && rope_cols % 256 == 0 && rope_cols >= 0 && rope_cols <= N,
+      "N and rope_cols must be multiples of 256 (a 256-column tile holds q / k heads or v heads)");
+  CHECK(check_ld(who, {lda, ldb, ldc}, {}));
+  CHECK(check_align(who, {A, B, C, cos_tab, sin_tab}, 16, "operands and tables"));
+  REQ(cos_tab && sin_tab && L > 0, "cos_tab, sin_tab and L > 0 required");
+  const EpiStoreRope epi{(bf16_t*)C, ldc, cos_tab, sin_tab, pos, L, rope_cols};
+  return launch_nn<EpiStoreRope, false, false, true>(shape(A, lda, B, ldb, M, N, K), epi, (hipStream_t)stream);
 }
 
 int rv_gemm_nn_swiglu_bf16(const void* A, long lda, const void* B, long ldb, void* GU, long ldgu, void* ACT, long ldact,
                            int M, int N, int K, void* stream) {
+  const char* const who = __func__;
   if (M == 0 || N == 0) return 0;
-  RV_REQUIRE(K > 0 && K % G2_BK == 0, "rv_gemm_nn_swiglu_bf16: K must be a positive multiple of 32");
-  RV_REQUIRE(N % 16 == 0, "rv_gemm_nn_swiglu_bf16: N (= 2 x ffn, interleaved gate/up columns) must be a multiple of 16");
-  RV_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && ldgu % 8 == 0 && ldact % 4 == 0, "rv_gemm_nn_swiglu_bf16: bad leading dimension");
-  RV_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)GU) & 15) == 0 && ((uintptr_t)ACT & 7) == 0,
-             "rv_gemm_nn_swiglu_bf16: operands must be 16-byte aligned (activation: 8)");
-  read_group_env();
-  GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group};
-  EpiSwiGLU epi{(bf16_t*)GU, ldgu, (bf16_t*)ACT, ldact};
-  return launch_nn_epi(g, epi, (hipStream_t)stream);
+  REQ(K > 0 && K % G2_BK == 0, "K must be a positive multiple of 32");
+  REQ(N % 16 == 0, "N (= 2 x ffn, interleaved gate/up columns) must be a multiple of 16");
+  CHECK(check_ld(who, {lda, ldb, ldgu}, {ldact}));
+  CHECK(check_align(who, {A, B, GU}, 16, "A/B/GU"));
+  CHECK(check_align(who, {ACT}, 8, "ACT"));
+  return launch_nn(shape(A, lda, B, ldb, M, N, K), EpiSwiGLU{(bf16_t*)GU, ldgu, (bf16_t*)ACT, ldact}, (hipStream_t)stream);
 }
 
 int rv_gemm_nn_swiglu_bwd_bf16(const void* A, long lda, const void* B, long ldb, const void* GU, long ldgu, void* DGU,
                                long lddgu, int M, int N, int K, void* stream) {
+  const char* const who = __func__;
   if (M == 0 || N == 0) return 0;
-  RV_REQUIRE(K > 0 && K % G2_BK == 0, "rv_gemm_nn_swiglu_bwd_bf16: K must be a positive multiple of 32");
-  RV_REQUIRE(N % 8 == 0, "rv_gemm_nn_swiglu_bwd_bf16: N (= ffn) must be a multiple of 8");
-  RV_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && ldgu % 8 == 0 && lddgu % 8 == 0, "rv_gemm_nn_swiglu_bwd_bf16: bad leading dimension");
-  RV_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)GU | (uintptr_t)DGU) & 15) == 0,
-             "rv_gemm_nn_swiglu_bwd_bf16: operands must be 16-byte aligned");
-  read_group_env();
-  GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group};
-  EpiSwiGLUBwd epi{(const bf16_t*)GU, ldgu, (bf16_t*)DGU, lddgu};
-  return launch_nn_epi(g, epi, (hipStream_t)stream);
+  REQ(K > 0 && K % G2_BK == 0, "K must be a positive multiple of 32");
+  REQ(N % 8 == 0, "N (= ffn) must be a multiple of 8");
+  CHECK(check_ld(who, {lda, ldb, ldgu, lddgu}, {}));
+  CHECK(check_align(who, {A, B, GU, DGU}, 16, "A/B/GU/DGU"));
+  return launch_nn(shape(A, lda, B, ldb, M, N, K), EpiSwiGLUBwd{(const bf16_t*)GU, ldgu, (bf16_t*)DGU, lddgu}, (hipStream_t)stream);
 }
 
 int rv_gemm_nn_lora_bf16(const void* A, long lda, const void* B, long ldb, const void* A2, long lda2, const void* B2,
                          long ldb2, int K2, int group_cols, int group0, void* C, long ldc, int M, int N, int K,
                          const void* residual, long ldr, void* stream) {
+  const char* const who = __func__;
   if (M == 0 || N == 0) return 0;
-  RV_REQUIRE(K > 0 && K % G2_BK == 0 && K2 > 0 && K2 % G2_BK == 0, "rv_gemm_nn_lora_bf16: K and K2 must be positive multiples of 32");
-  RV_REQUIRE(N % 8 == 0 && N >= 8, "rv_gemm_nn_lora_bf16: N must be a multiple of 8");
-  RV_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && lda2 % 8 == 0 && ldb2 % 8 == 0 && ldc % 4 == 0 && (residual == nullptr || ldr % 4 == 0),
-             "rv_gemm_nn_lora_bf16: leading dimensions must be multiples of 8 (inputs) / 4 (output)");
-  RV_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)A2 | (uintptr_t)B2) & 15) == 0,
-             "rv_gemm_nn_lora_bf16: operands must be 16-byte aligned");
-  RV_REQUIRE(group_cols == 0 || (group_cols % G2_BN == 0 && group0 % G2_BN == 0 && group0 >= 0 && group0 <= N &&
-                                 (N - (group0 ? group0 : group_cols)) % group_cols == 0),
-             "rv_gemm_nn_lora_bf16: group_cols / group0 must be multiples of 256 that tile N (group0 + k * group_cols = N)");
-  GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group,
-              (const bf16_t*)A2, (const bf16_t*)B2, lda2, ldb2, K2, group_cols, group0};
-  EpiStore epi{(bf16_t*)C, ldc, nullptr, (const bf16_t*)residual, ldr, RV_ACT_NONE, 1.0f};
-  epi.narrow = epi_narrow();
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_nn_256_kernel<EpiStore, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G2_LDS_BYTES);
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiStore, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiStore, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    attr_done = true;
-  }
-  const int tiles_m = (M + G2_BM - 1) / G2_BM, tiles_n = (N + G2_BN - 1) / G2_BN;
-  if (K % 64 == 0 && K2 % 64 == 0 && K >= 512 && nn_mi16())
-    hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiStore, true, true>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
-                       (hipStream_t)stream, g, epi);
-  else if (K % 64 == 0 && K2 % 64 == 0 && K >= 512)
-    hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiStore, true>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
-                       (hipStream_t)stream, g, epi);
-  else
-    hipLaunchKernelGGL((gemm_nn_256_kernel<EpiStore, true>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G2_LDS_BYTES,
-                       (hipStream_t)stream, g, epi);
-  RV_CHECK_LAUNCH();
+  REQ(K > 0 && K % G2_BK == 0 && K2 > 0 && K2 % G2_BK == 0, "K and K2 must be positive multiples of 32");
+  REQ(N % 8 == 0 && N >= 8, "N must be a multiple of 8");
+  CHECK(check_ld(who, {lda, ldb, lda2, ldb2}, {ldc, residual ? ldr : 0}));
+  CHECK(check_align(who, {A, B, A2, B2}, 16, "A/B/A2/B2"));
+  CHECK(check_groups(who, group_cols, group0, N, G2_BN));
+  const GemmShape g = shape_ext(A, lda, B, ldb, M, N, K, A2, lda2, B2, ldb2, K2, group_cols, group0);
+  return launch_nn<EpiStore, true>(g, epi_store(C, ldc, nullptr, residual, ldr, RV_ACT_NONE, 1.0f), (hipStream_t)stream);
+}
+
+// what the fused-adapter entries of the 64-deep-A kernel ask of K and K2
+static int check_a64_k(const char* who, int K, int K2) {
+  REQ(K >= 512 && K % 64 == 0 && K2 > 0 && K2 % 64 == 0, "K must be a multiple of 64 and >= 512, K2 a positive multiple of 64");
   return 0;
 }
 
@@ -536,38 +479,25 @@ int rv_gemm_nn_lora_bf16(const void* A, long lda, const void* B, long ldb, const
 int rv_gemm_nn_lora_swiglu_bf16(const void* A, long lda, const void* B, long ldb, const void* A2, long lda2, const void* B2,
                                 long ldb2, int K2, void* GU, long ldgu, void* ACT, long ldact, void* ACTD, float p, int seed,
                                 int M, int N, int K, void* stream) {
+  const char* const who = __func__;
   if (M == 0 || N == 0) return 0;
-  RV_REQUIRE(K >= 512 && K % 64 == 0 && K2 > 0 && K2 % 64 == 0, "rv_gemm_nn_lora_swiglu_bf16: K % 64, K >= 512, K2 % 64");
-  RV_REQUIRE(N % 16 == 0, "rv_gemm_nn_lora_swiglu_bf16: N (= 2 x ffn, interleaved gate/up columns) must be a multiple of 16");
-  RV_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && lda2 % 8 == 0 && ldb2 % 8 == 0 && ldgu % 8 == 0 && ldact % 4 == 0,
-             "rv_gemm_nn_lora_swiglu_bf16: bad leading dimension");
-  RV_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)A2 | (uintptr_t)B2 | (uintptr_t)GU) & 15) == 0 && ((uintptr_t)ACT & 7) == 0 &&
-             ((uintptr_t)ACTD & 7) == 0, "rv_gemm_nn_lora_swiglu_bf16: operands must be 16-byte aligned (activations: 8)");
-  RV_REQUIRE(p >= 0.f && p < 1.f && (ACTD == nullptr || ldact == N / 2), "rv_gemm_nn_lora_swiglu_bf16: 0 <= p < 1; ACTD needs a contiguous ACT");
-  read_group_env();
-  GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group, (const bf16_t*)A2, (const bf16_t*)B2, lda2, ldb2, K2, 0, 0};
+  CHECK(check_a64_k(who, K, K2));
+  REQ(N % 16 == 0, "N (= 2 x ffn, interleaved gate/up columns) must be a multiple of 16");
+  CHECK(check_ld(who, {lda, ldb, lda2, ldb2, ldgu}, {ldact}));
+  CHECK(check_align(who, {A, B, A2, B2, GU}, 16, "A/B/A2/B2/GU"));
+  CHECK(check_align(who, {ACT, ACTD}, 8, "ACT/ACTD"));
+  CHECK(check_p(who, p));
+  REQ(ACTD == nullptr || ldact == N / 2, "ACTD needs a contiguous ACT");
   EpiSwiGLU epi{(bf16_t*)GU, ldgu, (bf16_t*)ACT, ldact};
   if (ACTD != nullptr && p > 0.f) {
+    const DropParams d = drop_params(p, seed);
     epi.ACTD = (bf16_t*)ACTD;
-    epi.drop_thresh16 = (uint32_t)((double)p * 65536.0 + 0.5);
-    epi.drop_key = (uint32_t)seed * 0x9e3779b9u + 0x85ebca6bu;
-    epi.drop_inv_keep = 1.f / (1.f - p);
+    epi.drop_thresh16 = d.thresh16;
+    epi.drop_key = d.key;
+    epi.drop_inv_keep = d.inv_keep;
   }
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiSwiGLU, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiSwiGLU, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    attr_done = true;
-  }
-  const int tiles_m = (M + G2_BM - 1) / G2_BM, tiles_n = (N + G2_BN - 1) / G2_BN;
-  if (nn_mi16())
-    hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiSwiGLU, true, true>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
-                       (hipStream_t)stream, g, epi);
-  else
-    hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiSwiGLU, true>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
-                       (hipStream_t)stream, g, epi);
-  RV_CHECK_LAUNCH();
-  return 0;
+  const GemmShape g = shape_ext(A, lda, B, ldb, M, N, K, A2, lda2, B2, ldb2, K2, 0, 0);
+  return launch_nn<EpiSwiGLU, true, false, true>(g, epi, (hipStream_t)stream);
 }
 
 // Input gradient of an ADAPTER model's down projection with the SwiGLU backward in the epilogue: acc = d act = dy W + [mask](dt A) / (1 - p)
@@ -576,229 +506,196 @@ int rv_gemm_nn_lora_swiglu_bf16(const void* A, long lda, const void* B, long ldb
 int rv_gemm_nn_lora_swiglu_bwd_bf16(const void* A, long lda, const void* B, long ldb, const void* A2, long lda2, const void* B2,
                                     long ldb2, int K2, float p, int seed, const void* GU, long ldgu, void* DGU, long lddgu,
                                     int M, int N, int K, void* stream) {
+  const char* const who = __func__;
   if (M == 0 || N == 0) return 0;
-  RV_REQUIRE(K >= 512 && K % 64 == 0 && K2 > 0 && K2 % 64 == 0, "rv_gemm_nn_lora_swiglu_bwd_bf16: K % 64, K >= 512, K2 % 64");
-  RV_REQUIRE(N % 8 == 0, "rv_gemm_nn_lora_swiglu_bwd_bf16: N (= ffn) must be a multiple of 8");
-  RV_REQUIRE(p >= 0.f && p < 1.f, "rv_gemm_nn_lora_swiglu_bwd_bf16: 0 <= p < 1");
-  RV_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && lda2 % 8 == 0 && ldb2 % 8 == 0 && ldgu % 8 == 0 && lddgu % 8 == 0,
-             "rv_gemm_nn_lora_swiglu_bwd_bf16: bad leading dimension");
-  RV_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)A2 | (uintptr_t)B2 | (uintptr_t)GU | (uintptr_t)DGU) & 15) == 0,
-             "rv_gemm_nn_lora_swiglu_bwd_bf16: operands must be 16-byte aligned");
-  read_group_env();
-  GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group, (const bf16_t*)A2, (const bf16_t*)B2, lda2, ldb2, K2, 0, 0};
-  EpiSwiGLUBwd epi{(const bf16_t*)GU, ldgu, (bf16_t*)DGU, lddgu};
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiSwiGLUBwd, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiSwiGLUBwd, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiSwiGLUBwd, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiSwiGLUBwd, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    attr_done = true;
-  }
-  const int tiles_m = (M + G2_BM - 1) / G2_BM, tiles_n = (N + G2_BN - 1) / G2_BN;
-  const dim3 grid(tiles_m * tiles_n), block(G2_THREADS);
-  if (p > 0.f) {
-    g.pre_thresh16 = (uint32_t)((double)p * 65536.0 + 0.5);
-    g.pre_key = (uint32_t)seed * 0x9e3779b9u + 0x85ebca6bu;
-    g.pre_inv_keep = 1.f / (1.f - p);
-    if (nn_mi16()) hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiSwiGLUBwd, false, true, true>), grid, block, G4_LDS_BYTES, (hipStream_t)stream, g, epi);
-    else hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiSwiGLUBwd, false, false, true>), grid, block, G4_LDS_BYTES, (hipStream_t)stream, g, epi);
-  } else {
-    if (nn_mi16()) hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiSwiGLUBwd, true, true>), grid, block, G4_LDS_BYTES, (hipStream_t)stream, g, epi);
-    else hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiSwiGLUBwd, true>), grid, block, G4_LDS_BYTES, (hipStream_t)stream, g, epi);
-  }
-  RV_CHECK_LAUNCH();
-  return 0;
+  CHECK(check_a64_k(who, K, K2));
+  REQ(N % 8 == 0, "N (= ffn) must be a multiple of 8");
+  CHECK(check_p(who, p));
+  CHECK(check_ld(who, {lda, ldb, lda2, ldb2, ldgu, lddgu}, {}));
+  CHECK(check_align(who, {A, B, A2, B2, GU, DGU}, 16, "A/B/A2/B2/GU/DGU"));
+  GemmShape g = shape_ext(A, lda, B, ldb, M, N, K, A2, lda2, B2, ldb2, K2, 0, 0);
+  const EpiSwiGLUBwd epi{(const bf16_t*)GU, ldgu, (bf16_t*)DGU, lddgu};
+  if (p == 0.f) return launch_nn<EpiSwiGLUBwd, true, false, true>(g, epi, (hipStream_t)stream);
+  const DropParams d = drop_params(p, seed);
+  g.pre_thresh16 = d.thresh16;
+  g.pre_key = d.key;
+  g.pre_inv_keep = d.inv_keep;
+  return launch_nn<EpiSwiGLUBwd, false, true>(g, epi, (hipStream_t)stream);
 }
 
 int rv_gemm_nn_lora_pre_bf16(const void* A, long lda, const void* B, long ldb, const void* A2, long lda2, const void* B2,
                              long ldb2, int K2, int group_cols, int group0, float p, int seed, void* C, long ldc, int M, int N,
                              int K, const void* residual, long ldr, void* stream) {
+  const char* const who = __func__;
   if (M == 0 || N == 0) return 0;
-  RV_REQUIRE(K >= 512 && K % 64 == 0 && K2 > 0 && K2 % 64 == 0,
-             "rv_gemm_nn_lora_pre_bf16: K must be a multiple of 64 and >= 512, K2 a positive multiple of 64");
-  RV_REQUIRE(N % 8 == 0 && N >= 8, "rv_gemm_nn_lora_pre_bf16: N must be a multiple of 8 (mask layout of rv_dropout)");
-  RV_REQUIRE(p >= 0.f && p < 1.f, "rv_gemm_nn_lora_pre_bf16: 0 <= p < 1");
-  RV_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && lda2 % 8 == 0 && ldb2 % 8 == 0 && ldc % 4 == 0 && (residual == nullptr || ldr % 4 == 0),
-             "rv_gemm_nn_lora_pre_bf16: leading dimensions must be multiples of 8 (inputs) / 4 (output)");
-  RV_REQUIRE((((uintptr_t)A | (uintptr_t)B | (uintptr_t)A2 | (uintptr_t)B2) & 15) == 0,
-             "rv_gemm_nn_lora_pre_bf16: operands must be 16-byte aligned");
-  RV_REQUIRE(group_cols == 0 || (group_cols % G2_BN == 0 && group0 % G2_BN == 0 && group0 >= 0 && group0 <= N &&
-                                 (N - (group0 ? group0 : group_cols)) % group_cols == 0),
-             "rv_gemm_nn_lora_pre_bf16: group_cols / group0 must be multiples of 256 that tile N (group0 + k * group_cols = N)");
-  read_group_env();
-  GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group,
-              (const bf16_t*)A2, (const bf16_t*)B2, lda2, ldb2, K2, group_cols, group0};
-  g.pre_thresh16 = (uint32_t)((double)p * 65536.0 + 0.5);
-  g.pre_key = (uint32_t)seed * 0x9e3779b9u + 0x85ebca6bu;
-  g.pre_inv_keep = 1.f / (1.f - p);
-  EpiStore epi{(bf16_t*)C, ldc, nullptr, (const bf16_t*)residual, ldr, RV_ACT_NONE, 1.0f};
-  epi.narrow = epi_narrow();
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiStore, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    hipFuncSetAttribute((const void*)gemm_nn_a64_kernel<EpiStore, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, G4_LDS_BYTES);
-    attr_done = true;
-  }
-  const int tiles_m = (M + G2_BM - 1) / G2_BM, tiles_n = (N + G2_BN - 1) / G2_BN;
-  if (nn_mi16())
-    hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiStore, false, true, true>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
-                       (hipStream_t)stream, g, epi);
-  else
-    hipLaunchKernelGGL((gemm_nn_a64_kernel<EpiStore, false, false, true>), dim3(tiles_m * tiles_n), dim3(G2_THREADS), G4_LDS_BYTES,
-                       (hipStream_t)stream, g, epi);
-  RV_CHECK_LAUNCH();
-  return 0;
+  CHECK(check_a64_k(who, K, K2));
+  REQ(N % 8 == 0 && N >= 8, "N must be a multiple of 8 (mask layout of rv_dropout)");
+  CHECK(check_p(who, p));
+  CHECK(check_ld(who, {lda, ldb, lda2, ldb2}, {ldc, residual ? ldr : 0}));
+  CHECK(check_align(who, {A, B, A2, B2}, 16, "A/B/A2/B2"));
+  CHECK(check_groups(who, group_cols, group0, N, G2_BN));
+  GemmShape g = shape_ext(A, lda, B, ldb, M, N, K, A2, lda2, B2, ldb2, K2, group_cols, group0);
+  const DropParams d = drop_params(p, seed);
+  g.pre_thresh16 = d.thresh16;
+  g.pre_key = d.key;
+  g.pre_inv_keep = d.inv_keep;
+  return launch_nn<EpiStore, false, true>(g, epi_store(C, ldc, nullptr, residual, ldr, RV_ACT_NONE, 1.0f), (hipStream_t)stream);
 }
 
 int rv_gemm_nt_dropout_bf16(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
                             const void* residual, long ldr, float alpha, float p, int seed, void* stream) {
+  const char* const who = __func__;
   if (M == 0 || N == 0) return 0;
-  GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group};
-  if (check_shape(g, "rv_gemm_nt_dropout_bf16")) return 1;
-  RV_REQUIRE(p >= 0.f && p < 1.f, "rv_gemm_nt_dropout_bf16: 0 <= p < 1");
-  RV_REQUIRE(N % 8 == 0, "rv_gemm_nt_dropout_bf16: N must be a multiple of 8 (mask layout of rv_dropout)");
-  RV_REQUIRE(ldc % 4 == 0 && (residual == nullptr || ldr % 4 == 0), "rv_gemm_nt_dropout_bf16: ldc/ldr must be multiples of 4");
-  EpiStore epi{(bf16_t*)C, ldc, nullptr, (const bf16_t*)residual, ldr, RV_ACT_NONE, alpha};
-  epi.narrow = epi_narrow();
-  epi.drop_thresh16 = (uint32_t)((double)p * 65536.0 + 0.5);
-  epi.drop_key = (uint32_t)seed * 0x9e3779b9u + 0x85ebca6bu;
-  epi.drop_inv_keep = 1.f / (1.f - p);
-  return dispatch(g, epi, -1, stream);
+  const GemmShape g = shape(A, lda, B, ldb, M, N, K);
+  CHECK(check_shape(g, who));
+  CHECK(check_p(who, p));
+  REQ(N % 8 == 0, "N must be a multiple of 8 (mask layout of rv_dropout)");
+  CHECK(check_ld(who, {}, {ldc, residual ? ldr : 0}));
+  EpiStore epi = epi_store(C, ldc, nullptr, residual, ldr, RV_ACT_NONE, alpha);
+  const DropParams d = drop_params(p, seed);
+  epi.drop_thresh16 = d.thresh16;
+  epi.drop_key = d.key;
+  epi.drop_inv_keep = d.inv_keep;
+  return dispatch(who, g, epi, -1, stream);
 }
 
 int rv_gemm_tn_bf16_splitk(const void* P, long ldp, const void* Q, long ldq, void* C, long ldc, int R, int I, int J,
                            float alpha, int splits, float* workspace, void* stream) {
+  const char* const who = __func__;
   if (I == 0 || J == 0) return 0;
-  RV_REQUIRE(R > 0 && splits >= 1 && splits <= 1024, "rv_gemm_tn_bf16_splitk: R > 0, 1 <= splits <= 1024");
-  RV_REQUIRE(I % 8 == 0 && J % 8 == 0, "rv_gemm_tn_bf16_splitk: I and J must be multiples of 8");
-  RV_REQUIRE(ldp % 8 == 0 && ldq % 8 == 0 && ldc % 4 == 0, "rv_gemm_tn_bf16_splitk: bad leading dimension");
-  RV_REQUIRE((((uintptr_t)P | (uintptr_t)Q | (uintptr_t)workspace) & 15) == 0,
-             "rv_gemm_tn_bf16_splitk: P/Q/workspace must be 16-byte aligned");
-  RV_REQUIRE(workspace != nullptr, "rv_gemm_tn_bf16_splitk: workspace of splits*I*J floats required");
-  int r_chunk = ((R + splits - 1) / splits + 31) / 32 * 32;
-  splits = (R + r_chunk - 1) / r_chunk;            // no empty chunk
-  EpiStoreF32 epi{workspace, (long)J};
-  if (launch_gemm_tn((const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, R, I, J, epi, (hipStream_t)stream, splits, r_chunk,
-                     (long)I * J))
+  REQ(R > 0 && splits >= 1 && splits <= 1024, "R > 0, 1 <= splits <= 1024");
+  REQ(I % 8 == 0 && J % 8 == 0, "I and J must be multiples of 8");
+  CHECK(check_ld(who, {ldp, ldq}, {ldc}));
+  CHECK(check_align(who, {P, Q, workspace}, 16, "P/Q/workspace"));
+  REQ(workspace != nullptr, "workspace of splits*I*J floats required");
+  const SplitK s = splitk_chunks(R, splits);
+  if (launch_gemm_tn((const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, R, I, J, EpiStoreF32{workspace, (long)J}, (hipStream_t)stream, s.splits,
+                     s.r_chunk, (long)I * J))
     return 1;
-  const long n4 = (long)I * J / 4;
-  const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, workspace, splits, I, J, alpha,
-                     (bf16_t*)C, ldc);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch_splitk_reduce(workspace, s.splits, I, J, alpha, C, ldc, (hipStream_t)stream);
 }
 
 int rv_gemm_nt_lora_masks_bf16(const void* X, long ldx, const void* A, long lda, void* T, long ldt, int M, int K, int G,
                                float alpha, float p, int seed0, int seed1, int seed2, void* stream) {
-  RV_REQUIRE(G >= 1 && G <= 3, "rv_gemm_nt_lora_masks_bf16: 1 <= G <= 3 modules");
-  RV_REQUIRE(K > 0 && K % 64 == 0, "rv_gemm_nt_lora_masks_bf16: K must be a positive multiple of 64");
-  RV_REQUIRE(p >= 0.f && p < 1.f, "rv_gemm_nt_lora_masks_bf16: 0 <= p < 1");
-  RV_REQUIRE(M >= 0 && ldx >= K && lda >= K && ldx % 8 == 0 && lda % 8 == 0 && ldt >= G * 64 && ldt % 4 == 0,
-             "rv_gemm_nt_lora_masks_bf16: bad leading dimension (ldx, lda: multiples of 8, >= K; ldt: multiple of 4, >= 64 G)");
+  const char* const who = __func__;
+  REQ(G >= 1 && G <= 3, "1 <= G <= 3 modules");
+  REQ(K > 0 && K % 64 == 0, "K must be a positive multiple of 64");
+  CHECK(check_p(who, p));
+  CHECK(check_ld(who, {ldx, lda}, {ldt}));
+  REQ(M >= 0, "M must not be negative");
+  REQ(ldx >= K && lda >= K && ldt >= G * 64, "bad leading dimension (ldx, lda >= K; ldt >= 64 G)");
   if (M == 0) return 0;
-  RV_REQUIRE(X && A && T && (((uintptr_t)X | (uintptr_t)A) & 15) == 0 && ((uintptr_t)T & 7) == 0,
-             "rv_gemm_nt_lora_masks_bf16: X/A must be 16-byte aligned, T 8-byte aligned");
+  REQ(X && A && T, "X, A and T required");
+  CHECK(check_align(who, {X, A}, 16, "X/A"));
+  CHECK(check_align(who, {T}, 8, "T"));
   const LoraMasks dm = lora_masks(p, seed0, seed1, seed2);
-  const bf16_t *x = (const bf16_t*)X, *a = (const bf16_t*)A;
-  hipStream_t st = (hipStream_t)stream;
-  if (G == 1) return launch_lora_masks_fwd<1, 3>(x, ldx, a, lda, (bf16_t*)T, ldt, M, K, alpha, dm, st);
-  if (G == 2) return launch_lora_masks_fwd<2, 2>(x, ldx, a, lda, (bf16_t*)T, ldt, M, K, alpha, dm, st);
-  return launch_lora_masks_fwd<3, 2>(x, ldx, a, lda, (bf16_t*)T, ldt, M, K, alpha, dm, st);
+  return for_modules(G, [&](auto Gc) {
+    constexpr int G_ = decltype(Gc)::value, NST = G_ == 1 ? 3 : 2, LDS = NST * (16384 + G_ * 8192);
+    const dim3 grid((M + 127) / 128), block(256);
+    const bf16_t *x = (const bf16_t*)X, *a = (const bf16_t*)A;
+    if (dm.thresh16) return launch<lora_masks_fwd_kernel<G_, NST, true>>(LDS, grid, block, (hipStream_t)stream, x, ldx, a, lda, (bf16_t*)T, ldt, M, K, alpha, dm);
+    return launch<lora_masks_fwd_kernel<G_, NST, false>>(LDS, grid, block, (hipStream_t)stream, x, ldx, a, lda, (bf16_t*)T, ldt, M, K, alpha, dm);
+  });
 }
 
 int rv_gemm_nt_dropout_masks_bf16(const void* dT, long lddt, const void* AT, long ldat, void* C, long ldc, int M, int N, int G,
                                   const void* residual, long ldr, float p, int seed0, int seed1, int seed2, void* stream) {
-  RV_REQUIRE(G >= 1 && G <= 3, "rv_gemm_nt_dropout_masks_bf16: 1 <= G <= 3 modules");
-  RV_REQUIRE(N > 0 && N % 64 == 0, "rv_gemm_nt_dropout_masks_bf16: N must be a positive multiple of 64");
-  RV_REQUIRE(p >= 0.f && p < 1.f, "rv_gemm_nt_dropout_masks_bf16: 0 <= p < 1");
-  RV_REQUIRE(M >= 0 && lddt >= G * 64 && ldat >= G * 64 && lddt % 8 == 0 && ldat % 8 == 0 && ldc >= N && ldc % 4 == 0 &&
-                 (residual == nullptr || (ldr >= N && ldr % 4 == 0)),
-             "rv_gemm_nt_dropout_masks_bf16: bad leading dimension (lddt, ldat: multiples of 8, >= 64 G; ldc, ldr: multiples of 4, >= N)");
+  const char* const who = __func__;
+  REQ(G >= 1 && G <= 3, "1 <= G <= 3 modules");
+  REQ(N > 0 && N % 64 == 0, "N must be a positive multiple of 64");
+  CHECK(check_p(who, p));
+  CHECK(check_ld(who, {lddt, ldat}, {ldc, residual ? ldr : 0}));
+  REQ(M >= 0, "M must not be negative");
+  REQ(lddt >= G * 64 && ldat >= G * 64 && ldc >= N && (residual == nullptr || ldr >= N),
+      "bad leading dimension (lddt, ldat >= 64 G; ldc, ldr >= N)");
   if (M == 0) return 0;
-  RV_REQUIRE(dT && AT && C && (((uintptr_t)dT | (uintptr_t)AT) & 15) == 0 && (((uintptr_t)C | (uintptr_t)residual) & 7) == 0,
-             "rv_gemm_nt_dropout_masks_bf16: dT/AT must be 16-byte aligned, C/residual 8-byte aligned");
+  REQ(dT && AT && C, "dT, AT and C required");
+  CHECK(check_align(who, {dT, AT}, 16, "dT/AT"));
+  CHECK(check_align(who, {C, residual}, 8, "C/residual"));
   // one module: exactly rv_gemm_nt_dropout_bf16 (same kernels, same bits)
   if (G == 1) return rv_gemm_nt_dropout_bf16(dT, lddt, AT, ldat, C, ldc, M, N, 64, residual, ldr, 1.0f, p, seed0, stream);
   const LoraMasks dm = lora_masks(p, seed0, seed1, seed2);
-  if (G == 2)
-    return launch_lora_masks_dgrad<2>((const bf16_t*)dT, lddt, (const bf16_t*)AT, ldat, (bf16_t*)C, ldc, (const bf16_t*)residual, ldr, M, N,
-                                      dm, (hipStream_t)stream);
-  return launch_lora_masks_dgrad<3>((const bf16_t*)dT, lddt, (const bf16_t*)AT, ldat, (bf16_t*)C, ldc, (const bf16_t*)residual, ldr, M, N, dm,
-                                    (hipStream_t)stream);
+  return for_modules<2>(G, [&](auto Gc) {
+    constexpr int G_ = decltype(Gc)::value;
+    const dim3 grid(tiles(M, GEMM_BM) * tiles(N, GEMM_BN)), block(GEMM_THREADS);
+    const bf16_t *dt = (const bf16_t*)dT, *at = (const bf16_t*)AT, *r = (const bf16_t*)residual;
+    if (dm.thresh16) return launch<lora_masks_dgrad_kernel<G_, true>>(GEMM_LDS_BYTES, grid, block, (hipStream_t)stream, dt, lddt, at, ldat, (bf16_t*)C, ldc, r, ldr, M, N, dm);
+    return launch<lora_masks_dgrad_kernel<G_, false>>(GEMM_LDS_BYTES, grid, block, (hipStream_t)stream, dt, lddt, at, ldat, (bf16_t*)C, ldc, r, ldr, M, N, dm);
+  });
 }
 
 int rv_gemm_tn_lora_masks_bf16(const void* dT, long lddt, const void* X, long ldx, void* dA, long ldda, int R, int K, int G, float p,
                                int seed0, int seed1, int seed2, int splits, float* workspace, void* stream) {
-  RV_REQUIRE(G >= 1 && G <= 3, "rv_gemm_tn_lora_masks_bf16: 1 <= G <= 3 modules");
-  RV_REQUIRE(K > 0 && K % 64 == 0, "rv_gemm_tn_lora_masks_bf16: K must be a positive multiple of 64");
-  RV_REQUIRE(p >= 0.f && p < 1.f, "rv_gemm_tn_lora_masks_bf16: 0 <= p < 1");
-  RV_REQUIRE(R > 0 && splits >= 1 && splits <= 1024, "rv_gemm_tn_lora_masks_bf16: R > 0, 1 <= splits <= 1024");
-  RV_REQUIRE(lddt >= G * 64 && ldx >= K && lddt % 8 == 0 && ldx % 8 == 0 && ldda >= K && ldda % 4 == 0,
-             "rv_gemm_tn_lora_masks_bf16: bad leading dimension (lddt: multiple of 8, >= 64 G; ldx: multiple of 8, >= K; ldda: multiple of 4, >= K)");
-  RV_REQUIRE(dT && X && dA && (((uintptr_t)dT | (uintptr_t)X | (uintptr_t)workspace) & 15) == 0 && ((uintptr_t)dA & 7) == 0,
-             "rv_gemm_tn_lora_masks_bf16: dT/X/workspace must be 16-byte aligned, dA 8-byte aligned");
-  RV_REQUIRE(workspace != nullptr, "rv_gemm_tn_lora_masks_bf16: workspace of splits * 64 G * K floats required");
+  const char* const who = __func__;
+  REQ(G >= 1 && G <= 3, "1 <= G <= 3 modules");
+  REQ(K > 0 && K % 64 == 0, "K must be a positive multiple of 64");
+  CHECK(check_p(who, p));
+  REQ(R > 0 && splits >= 1 && splits <= 1024, "R > 0, 1 <= splits <= 1024");
+  CHECK(check_ld(who, {lddt, ldx}, {ldda}));
+  REQ(lddt >= G * 64 && ldx >= K && ldda >= K, "bad leading dimension (lddt >= 64 G; ldx, ldda >= K)");
+  REQ(dT && X && dA, "dT, X and dA required");
+  CHECK(check_align(who, {dT, X, workspace}, 16, "dT/X/workspace"));
+  CHECK(check_align(who, {dA}, 8, "dA"));
+  REQ(workspace != nullptr, "workspace of splits * 64 G * K floats required");
   // p = 0: the plain split-K weight gradient
   if (p == 0.f) return rv_gemm_tn_bf16_splitk(dT, lddt, X, ldx, dA, ldda, R, G * 64, K, 1.0f, splits, workspace, stream);
-  const int r_chunk = ((R + splits - 1) / splits + 31) / 32 * 32;
-  splits = (R + r_chunk - 1) / r_chunk;            // no empty chunk
+  const SplitK s = splitk_chunks(R, splits);
   const LoraMasks dm = lora_masks(p, seed0, seed1, seed2);
-  const dim3 grid((K + LMW_JT - 1) / LMW_JT, splits), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (G == 1) hipLaunchKernelGGL(lora_masks_wgrad_kernel<1>, grid, block, 0, st, (const bf16_t*)dT, lddt, (const bf16_t*)X, ldx, workspace, R, K, r_chunk, dm);
-  else if (G == 2) hipLaunchKernelGGL(lora_masks_wgrad_kernel<2>, grid, block, 0, st, (const bf16_t*)dT, lddt, (const bf16_t*)X, ldx, workspace, R, K, r_chunk, dm);
-  else hipLaunchKernelGGL(lora_masks_wgrad_kernel<3>, grid, block, 0, st, (const bf16_t*)dT, lddt, (const bf16_t*)X, ldx, workspace, R, K, r_chunk, dm);
-  RV_CHECK_LAUNCH();
-  const long n4 = (long)G * 64 * K / 4;
-  const int blocks = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, workspace, splits, G * 64, K, 1.0f, (bf16_t*)dA, ldda);
-  RV_CHECK_LAUNCH();
-  return 0;
+  const int rc = for_modules(G, [&](auto Gc) {
+    return launch<lora_masks_wgrad_kernel<decltype(Gc)::value>>(0, dim3(tiles(K, LMW_JT), s.splits), dim3(256), (hipStream_t)stream,
+                                                               (const bf16_t*)dT, lddt, (const bf16_t*)X, ldx, workspace, R, K, s.r_chunk, dm);
+  });
+  if (rc) return rc;
+  return launch_splitk_reduce(workspace, s.splits, G * 64, K, 1.0f, dA, ldda, (hipStream_t)stream);
 }
 
 int rv_gemm_nt_bf16_f32out(const void* A, long lda, const void* B, long ldb, float* C, long ldc, int M, int N, int K,
                            int variant, void* stream) {
+  const char* const who = __func__;
   if (M == 0 || N == 0) return 0;
-  GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group};
-  if (check_shape(g, "rv_gemm_nt_bf16_f32out")) return 1;
-  RV_REQUIRE(ldc % 4 == 0, "rv_gemm_nt_bf16_f32out: ldc must be a multiple of 4");
-  EpiStoreF32 epi{C, ldc};
-  return dispatch(g, epi, variant, stream);
+  const GemmShape g = shape(A, lda, B, ldb, M, N, K);
+  CHECK(check_shape(g, who));
+  CHECK(check_ld(who, {}, {ldc}));
+  return dispatch(who, g, EpiStoreF32{C, ldc}, variant, stream);
 }
 
 int rv_gemm_nt_bf16_f32res(const void* A, long lda, const void* B, long ldb, float* C, long ldc, int M, int N, int K,
                            const void* bias, const float* residual, long ldr, int variant, void* stream) {
+  const char* const who = __func__;
   if (M == 0 || N == 0) return 0;
-  GemmShape g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, g_group};
-  if (check_shape(g, "rv_gemm_nt_bf16_f32res")) return 1;
-  RV_REQUIRE(ldc % 4 == 0 && ldr % 4 == 0, "rv_gemm_nt_bf16_f32res: ldc / ldr must be multiples of 4");
-  EpiStoreF32 epi{C, ldc, (const bf16_t*)bias, residual, ldr};
-  return dispatch(g, epi, variant, stream);
+  const GemmShape g = shape(A, lda, B, ldb, M, N, K);
+  CHECK(check_shape(g, who));
+  CHECK(check_ld(who, {}, {ldc, ldr}));
+  return dispatch(who, g, EpiStoreF32{C, ldc, (const bf16_t*)bias, residual, ldr}, variant, stream);
+}
+
+// the vocabulary bounds of the LM-head kernels
+static int check_vocab(const char* who, int V, int V_valid) {
+  REQ(V_valid > V - 64 && V_valid <= V, "V - 64 < V_valid <= V");
+  return 0;
 }
 
 int rv_lmhead_logp_fwd(const void* h, long ldh, const void* W, long ldw, const int* tgt, int M, int V, int V_valid, int K,
                        float* pmax, float* psum, float* tgt_logit, int variant, void* stream) {
+  const char* const who = __func__;
   if (M == 0) return 0;
-  GemmShape g{(const bf16_t*)h, (const bf16_t*)W, M, V, K, ldh, ldw, g_group};
-  if (check_shape(g, "rv_lmhead_logp_fwd")) return 1;
-  RV_REQUIRE(V % 64 == 0, "rv_lmhead_logp_fwd: the STORED vocabulary (rows of W) must be a multiple of 64; pad with zero rows");
-  RV_REQUIRE(V_valid > V - 64 && V_valid <= V, "rv_lmhead_logp_fwd: V - 64 < V_valid <= V");
-  EpiLogpFwd epi{tgt, pmax, psum, tgt_logit, V_valid};
-  return dispatch(g, epi, variant, stream);
+  const GemmShape g = shape(h, ldh, W, ldw, M, V, K);
+  CHECK(check_shape(g, who));
+  REQ(V % 64 == 0, "V, the STORED vocabulary (rows of W), must be a multiple of 64; pad with zero rows");
+  CHECK(check_vocab(who, V, V_valid));
+  return dispatch(who, g, EpiLogpFwd{tgt, pmax, psum, tgt_logit, V_valid}, variant, stream);
 }
 
 int rv_lmhead_logp_bwd(const void* h, long ldh, const void* W, long ldw, const int* tgt, const float* lse,
                        const float* coef, void* dlogits, long ldd, int M, int V, int V_valid, int K, int variant,
                        void* stream) {
+  const char* const who = __func__;
   if (M == 0) return 0;
-  GemmShape g{(const bf16_t*)h, (const bf16_t*)W, M, V, K, ldh, ldw, g_group};
-  if (check_shape(g, "rv_lmhead_logp_bwd")) return 1;
-  RV_REQUIRE(ldd % 4 == 0, "rv_lmhead_logp_bwd: ldd must be a multiple of 4");
-  RV_REQUIRE(V_valid > V - 64 && V_valid <= V, "rv_lmhead_logp_bwd: V - 64 < V_valid <= V");
-  EpiLogpBwd epi{tgt, lse, coef, (bf16_t*)dlogits, ldd, V_valid};
-  return dispatch(g, epi, variant, stream);
+  const GemmShape g = shape(h, ldh, W, ldw, M, V, K);
+  CHECK(check_shape(g, who));
+  CHECK(check_ld(who, {}, {ldd}));
+  CHECK(check_vocab(who, V, V_valid));
+  return dispatch(who, g, EpiLogpBwd{tgt, lse, coef, (bf16_t*)dlogits, ldd, V_valid}, variant, stream);
 }
 
 }  // extern "C"

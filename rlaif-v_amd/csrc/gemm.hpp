@@ -49,21 +49,15 @@ struct GemmShape {
   float pre_inv_keep = 1.f;
 };
 
-__device__ __forceinline__ uint32_t gemm_mix32(uint32_t h) {    // same mixer as dropout_kernel (elementwise.hip)
-  h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
-  return h;
-}
-
 // rv_dropout's keep decision for the 4 consecutive elements (m, n .. n+3), n % 4 == 0, of a contiguous [M][N] tensor (N % 8 == 0)
 __device__ __forceinline__ f32x4_t gemm_dropmask4(f32x4_t v, long m, int n, int N, uint32_t thresh16, uint32_t key, float inv_keep) {
   const long e = m * N + n;
-  const uint32_t base = (uint32_t)(e >> 33) * 0x9e3779b9u + key;
-  const uint32_t h0 = gemm_mix32((uint32_t)(e >> 1) ^ base), h1 = gemm_mix32(((uint32_t)(e >> 1) + 1u) ^ base);
-  v.x = ((h0 & 0xffffu) >= thresh16) ? v.x * inv_keep : 0.f;
-  v.y = ((h0 >> 16) >= thresh16) ? v.y * inv_keep : 0.f;
-  v.z = ((h1 & 0xffffu) >= thresh16) ? v.z * inv_keep : 0.f;
-  v.w = ((h1 >> 16) >= thresh16) ? v.w * inv_keep : 0.f;
-  return v;
+  const uint32_t base = drop_base((uint32_t)(e >> 33), key);
+  const uint32_t h0 = drop_pair_bits((uint32_t)(e >> 1), base), h1 = drop_pair_bits((uint32_t)(e >> 1) + 1u, base);
+  float f[4] = {v.x, v.y, v.z, v.w};
+  drop_keep2(h0, thresh16, inv_keep, f[0], f[1]);
+  drop_keep2(h1, thresh16, inv_keep, f[2], f[3]);
+  return f32x4_t{f[0], f[1], f[2], f[3]};
 }
 
 __device__ __forceinline__ int ext_group(int n0, int group0, int group_cols) {
@@ -1417,13 +1411,10 @@ struct EpiStore {
           }
           if (drop_thresh16) {
             const long e = (long)m * N + n;
-            const uint32_t base = (uint32_t)(e >> 33) * 0x9e3779b9u + drop_key;
+            const uint32_t base = drop_base((uint32_t)(e >> 33), drop_key);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const uint32_t h = gemm_mix32(((uint32_t)(e >> 1) + (uint32_t)q) ^ base);
-              v[2 * q] = ((h & 0xffffu) >= drop_thresh16) ? v[2 * q] * drop_inv_keep : 0.f;
-              v[2 * q + 1] = ((h >> 16) >= drop_thresh16) ? v[2 * q + 1] * drop_inv_keep : 0.f;
-            }
+            for (int q = 0; q < 4; ++q)
+              drop_keep2(drop_pair_bits((uint32_t)(e >> 1) + (uint32_t)q, base), drop_thresh16, drop_inv_keep, v[2 * q], v[2 * q + 1]);
           }
           if (R) {
             float rr[8];
@@ -1469,12 +1460,10 @@ struct EpiStore {
           }
           if (drop_thresh16) {
             const long e = (long)m * N + n;                               // element index in the logical [M][N] tensor
-            const uint32_t base = (uint32_t)(e >> 33) * 0x9e3779b9u + drop_key;
-            const uint32_t h0 = gemm_mix32((uint32_t)(e >> 1) ^ base), h1 = gemm_mix32(((uint32_t)(e >> 1) + 1u) ^ base);
-            v[0] = ((h0 & 0xffffu) >= drop_thresh16) ? v[0] * drop_inv_keep : 0.f;
-            v[1] = ((h0 >> 16) >= drop_thresh16) ? v[1] * drop_inv_keep : 0.f;
-            v[2] = ((h1 & 0xffffu) >= drop_thresh16) ? v[2] * drop_inv_keep : 0.f;
-            v[3] = ((h1 >> 16) >= drop_thresh16) ? v[3] * drop_inv_keep : 0.f;
+            const uint32_t base = drop_base((uint32_t)(e >> 33), drop_key);
+            const uint32_t h0 = drop_pair_bits((uint32_t)(e >> 1), base), h1 = drop_pair_bits((uint32_t)(e >> 1) + 1u, base);
+            drop_keep2(h0, drop_thresh16, drop_inv_keep, v[0], v[1]);
+            drop_keep2(h1, drop_thresh16, drop_inv_keep, v[2], v[3]);
           }
           if (R) {
             const uint2 rr = *(const uint2*)(R + (long)m * ldr + n);
@@ -1608,11 +1597,11 @@ struct EpiSwiGLU {
           *(uint2*)(ACT + (long)m * lda + (n >> 1)) = w;
           if (ACTD) {                   // rv_dropout's arithmetic on the ROUNDED activation (mask index = element index in [M][N/2])
             const long e = (long)m * (N >> 1) + (n >> 1);
-            const uint32_t base = (uint32_t)(e >> 33) * 0x9e3779b9u + drop_key;
-            const uint32_t h0 = gemm_mix32((uint32_t)(e >> 1) ^ base), h1 = gemm_mix32(((uint32_t)(e >> 1) + 1u) ^ base);
+            const uint32_t base = drop_base((uint32_t)(e >> 33), drop_key);
+            const uint32_t h0 = drop_pair_bits((uint32_t)(e >> 1), base), h1 = drop_pair_bits((uint32_t)(e >> 1) + 1u, base);
             const float a0 = bf2f((bf16_t)(w.x & 0xffff)), a1 = bf2f((bf16_t)(w.x >> 16));
             const float a2 = bf2f((bf16_t)(w.y & 0xffff)), a3 = bf2f((bf16_t)(w.y >> 16));
-            uint2 wd;
+            uint2 wd;       // (drop_keep2 on a0 .. a3 and then the two packs schedules differently: the keep decision stays written out)
             wd.x = pack2bf(((h0 & 0xffffu) >= drop_thresh16) ? a0 * drop_inv_keep : 0.f, ((h0 >> 16) >= drop_thresh16) ? a1 * drop_inv_keep : 0.f);
             wd.y = pack2bf(((h1 & 0xffffu) >= drop_thresh16) ? a2 * drop_inv_keep : 0.f, ((h1 >> 16) >= drop_thresh16) ? a3 * drop_inv_keep : 0.f);
             *(uint2*)(ACTD + (long)m * (N >> 1) + (n >> 1)) = wd;
@@ -1831,11 +1820,11 @@ __device__ __forceinline__ u32x4_t lora_scale_chunk(u32x4_t v, float inv_keep) {
 }
 // ... and the per-module half: zero the dropped elements of 16-byte chunk i8 (= element index / 8) of the contiguous tensor
 __device__ __forceinline__ u32x4_t lora_mask_chunk(u32x4_t scaled, long i8, uint32_t thresh16, uint32_t key) {
-  const uint32_t base = (uint32_t)(i8 >> 30) * 0x9e3779b9u + key;
+  const uint32_t base = drop_base((uint32_t)(i8 >> 30), key);
   const uint32_t i4 = (uint32_t)i8 * 4u;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const uint32_t h = gemm_mix32((i4 + (uint32_t)j) ^ base);
+    const uint32_t h = drop_pair_bits(i4 + (uint32_t)j, base);
     scaled[j] &= (((h & 0xffffu) >= thresh16) ? 0x0000ffffu : 0u) | (((h >> 16) >= thresh16) ? 0xffff0000u : 0u);
   }
   return scaled;

@@ -28,6 +28,30 @@ def round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
+def _out(out: Optional[torch.Tensor], M: int, N: int, like: torch.Tensor) -> torch.Tensor:
+    """The bf16 [M, N] result of a GEMM wrapper: a new tensor on ``like``'s device, or the caller's ``out`` after _chk2d."""
+    if out is None:
+        return torch.empty(M, N, dtype=BF16, device=like.device)
+    _chk2d(out, "out")
+    return out
+
+
+def _ld(t: Optional[torch.Tensor]) -> int:
+    """Leading dimension of an optional operand (0 when it is absent)."""
+    return t.stride(0) if t is not None else 0
+
+
+def _fills_chip(M: int, N: int) -> bool:
+    """Whether an [M, N] output fills the chip with 256 x 256 tiles: from 192 tiles on the library runs its 256-tile kernels
+    (fills_chip / dispatch() in csrc/gemm.hip), and the wrappers route to the NN kernels on the transposed weight."""
+    return ((M + 255) // 256) * ((N + 255) // 256) >= 192
+
+
+def _seed31(seed) -> int:
+    """A dropout seed as the non-negative C int the ABI takes."""
+    return int(seed) & 0x7FFFFFFF
+
+
 # ------------------------------------------------------------------------------------- GEMM
 def gemm_nt(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
             residual: Optional[torch.Tensor] = None, act: int = ACT_NONE, alpha: float = 1.0,
@@ -38,13 +62,11 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None
     N, Kb = b.shape
     if K != Kb:
         raise ValueError(f"gemm_nt: K mismatch {K} vs {Kb}")
-    if out is None:
-        out = torch.empty(M, N, dtype=BF16, device=a.device)
-    _chk2d(out, "out")
+    out = _out(out, M, N, a)
     if residual is not None:
         _chk2d(residual, "residual")
-    hip.call("rv_gemm_nt_bf16", a, a.stride(0), b, b.stride(0), out, out.stride(0), M, N, K, bias, residual,
-             residual.stride(0) if residual is not None else 0, act, float(alpha), variant)
+    hip.call("rv_gemm_nt_bf16", a, a.stride(0), b, b.stride(0), out, out.stride(0), M, N, K, bias, residual, _ld(residual), act,
+             float(alpha), variant)
     return out
 
 
@@ -58,15 +80,12 @@ def gemm_nn(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None
     Kb, N = b.shape
     if K != Kb:
         raise ValueError(f"gemm_nn: inner dimensions differ: {K} vs {Kb}")
-    if out is None:
-        out = torch.empty(M, N, dtype=BF16, device=a.device)
-    _chk2d(out, "out")
+    out = _out(out, M, N, a)
     if bias is not None or act != ACT_NONE:
         hip.call("rv_gemm_nn_bias_act_bf16", a, a.stride(0), b, b.stride(0), out, out.stride(0), M, N, K, bias, residual,
-                 residual.stride(0) if residual is not None else 0, int(act), float(alpha))
+                 _ld(residual), int(act), float(alpha))
         return out
-    hip.call("rv_gemm_nn_bf16", a, a.stride(0), b, b.stride(0), out, out.stride(0), M, N, K, residual,
-             residual.stride(0) if residual is not None else 0, float(alpha))
+    hip.call("rv_gemm_nn_bf16", a, a.stride(0), b, b.stride(0), out, out.stride(0), M, N, K, residual, _ld(residual), float(alpha))
     return out
 
 
@@ -76,15 +95,14 @@ def linear(x: torch.Tensor, w: torch.Tensor, wT: Optional[torch.Tensor], residua
     the chip with 256x256 tiles take the NN kernel on wT - its weight tile is fetched in full 512-byte segments
     (+6-12 % over the NT kernel on the 7B shapes); small ones take the NT kernels on w."""
     M, N = x.shape[0], w.shape[0]
-    if wT is not None and ((M + 255) // 256) * ((N + 255) // 256) >= 192 and x.shape[1] % 32 == 0 and N % 8 == 0:
+    if wT is not None and _fills_chip(M, N) and x.shape[1] % 32 == 0 and N % 8 == 0:
         return gemm_nn(x, wT[:, :N], out=out, residual=residual)
     return gemm_nt(x, w, out=out, residual=residual)
 
 
 def linear_rope_ok(M: int, N: int, K: int, rope_cols: int, hd: int) -> bool:
     """Whether ``linear_rope`` serves this q|k|v projection (else: ``linear`` + ``rope_inplace``)."""
-    return (hd == 128 and N % 256 == 0 and rope_cols % 256 == 0 and K % 64 == 0 and K >= 512
-            and ((M + 255) // 256) * (N // 256) >= 192)
+    return hd == 128 and N % 256 == 0 and rope_cols % 256 == 0 and K % 64 == 0 and K >= 512 and _fills_chip(M, N)
 
 
 def linear_rope(x: torch.Tensor, wT: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: Optional[torch.Tensor], L: int,
@@ -109,9 +127,7 @@ def gemm_tn(p: torch.Tensor, q: torch.Tensor, out: Optional[torch.Tensor] = None
     Rq, J = q.shape
     if R != Rq:
         raise ValueError(f"gemm_tn: row mismatch {R} vs {Rq}")
-    if out is None:
-        out = torch.empty(I, J, dtype=BF16, device=p.device)
-    _chk2d(out, "out")
+    out = _out(out, I, J, p)
     if residual is None and alpha == 1.0:
         # weight gradients: the partly filled last round of 256 tiles is split over the token axis (rv_gemm_tn_bf16_ws)
         need = _TN_WS_NEED.get((R, I, J))
@@ -124,8 +140,7 @@ def gemm_tn(p: torch.Tensor, q: torch.Tensor, out: Optional[torch.Tensor] = None
             ws = torch.empty(need, dtype=torch.float32, device=p.device)
             hip.call("rv_gemm_tn_bf16_ws", p, p.stride(0), q, q.stride(0), out, out.stride(0), R, I, J, ws, ws.numel())
             return out
-    hip.call("rv_gemm_tn_bf16", p, p.stride(0), q, q.stride(0), out, out.stride(0), R, I, J, residual,
-             residual.stride(0) if residual is not None else 0, float(alpha))
+    hip.call("rv_gemm_tn_bf16", p, p.stride(0), q, q.stride(0), out, out.stride(0), R, I, J, residual, _ld(residual), float(alpha))
     return out
 
 
@@ -143,43 +158,34 @@ def _lora_groups(N: int, group_cols: int, group0: int) -> int:
     return 1 + (N - g0) // group_cols
 
 
+def _gemm_lora(nn: bool, a, b, a2, b2, group_cols, out, residual, group0) -> torch.Tensor:
+    """gemm_nt_lora (b [N, K], b2 [N, K2]) and gemm_nn_lora (b [K, N], b2 [K2, N]): one validation, one call."""
+    who = "gemm_nn_lora" if nn else "gemm_nt_lora"
+    _chk2d(a, "a"), _chk2d(b, "b"), _chk2d(a2, "a2"), _chk2d(b2, "b2")
+    M, K = a.shape
+    K2, N = b2.shape if nn else b2.shape[::-1]
+    if b.shape != ((K, N) if nn else (N, K)) or a2.shape[0] != M:
+        raise ValueError(f"{who}: shape mismatch a{tuple(a.shape)} b{tuple(b.shape)} a2{tuple(a2.shape)} b2{tuple(b2.shape)}")
+    groups = _lora_groups(N, group_cols, group0)
+    if a2.shape[1] != groups * K2:
+        raise ValueError(f"{who}: a2 must have {groups} x {K2} columns, got {a2.shape[1]}")
+    out = _out(out, M, N, a)
+    hip.call("rv_gemm_nn_lora_bf16" if nn else "rv_gemm_nt_lora_bf16", a, a.stride(0), b, b.stride(0), a2, a2.stride(0), b2,
+             b2.stride(0), K2, int(group_cols), int(group0), out, out.stride(0), M, N, K, residual, _ld(residual))
+    return out
+
+
 def gemm_nt_lora(a: torch.Tensor, b: torch.Tensor, a2: torch.Tensor, b2: torch.Tensor, group_cols: int = 0,
                  out: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, group0: int = 0) -> torch.Tensor:
     """out = a @ b^T + a2[:, c0(n) : c0(n)+K2] @ b2^T (+ residual): the fused LoRA GEMM (rv_gemm_nt_lora_bf16).
     K2 = b2.shape[1]; c0(n) = group(n) * K2 when group_cols > 0 (fused q|k|v, gate|up; _lora_groups), else 0."""
-    _chk2d(a, "a"), _chk2d(b, "b"), _chk2d(a2, "a2"), _chk2d(b2, "b2")
-    M, K = a.shape
-    N, K2 = b2.shape
-    if b.shape != (N, K) or a2.shape[0] != M:
-        raise ValueError(f"gemm_nt_lora: shape mismatch a{tuple(a.shape)} b{tuple(b.shape)} a2{tuple(a2.shape)} b2{tuple(b2.shape)}")
-    groups = _lora_groups(N, group_cols, group0)
-    if a2.shape[1] != groups * K2:
-        raise ValueError(f"gemm_nt_lora: a2 must have {groups} x {K2} columns, got {a2.shape[1]}")
-    if out is None:
-        out = torch.empty(M, N, dtype=BF16, device=a.device)
-    _chk2d(out, "out")
-    hip.call("rv_gemm_nt_lora_bf16", a, a.stride(0), b, b.stride(0), a2, a2.stride(0), b2, b2.stride(0), K2,
-             int(group_cols), int(group0), out, out.stride(0), M, N, K, residual, residual.stride(0) if residual is not None else 0)
-    return out
+    return _gemm_lora(False, a, b, a2, b2, group_cols, out, residual, group0)
 
 
 def gemm_nn_lora(a: torch.Tensor, b: torch.Tensor, a2: torch.Tensor, b2: torch.Tensor, group_cols: int = 0,
                  out: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, group0: int = 0) -> torch.Tensor:
     """NN form of gemm_nt_lora: b [K, N] and b2 [K2, N] row-major (rv_gemm_nn_lora_bf16)."""
-    _chk2d(a, "a"), _chk2d(b, "b"), _chk2d(a2, "a2"), _chk2d(b2, "b2")
-    M, K = a.shape
-    K2, N = b2.shape
-    if b.shape != (K, N) or a2.shape[0] != M:
-        raise ValueError(f"gemm_nn_lora: shape mismatch a{tuple(a.shape)} b{tuple(b.shape)} a2{tuple(a2.shape)} b2{tuple(b2.shape)}")
-    groups = _lora_groups(N, group_cols, group0)
-    if a2.shape[1] != groups * K2:
-        raise ValueError(f"gemm_nn_lora: a2 must have {groups} x {K2} columns, got {a2.shape[1]}")
-    if out is None:
-        out = torch.empty(M, N, dtype=BF16, device=a.device)
-    _chk2d(out, "out")
-    hip.call("rv_gemm_nn_lora_bf16", a, a.stride(0), b, b.stride(0), a2, a2.stride(0), b2, b2.stride(0), K2,
-             int(group_cols), int(group0), out, out.stride(0), M, N, K, residual, residual.stride(0) if residual is not None else 0)
-    return out
+    return _gemm_lora(True, a, b, a2, b2, group_cols, out, residual, group0)
 
 
 def linear_lora(x: torch.Tensor, w: torch.Tensor, wT: torch.Tensor, a2: torch.Tensor, b2: torch.Tensor, b2T: torch.Tensor,
@@ -187,7 +193,7 @@ def linear_lora(x: torch.Tensor, w: torch.Tensor, wT: torch.Tensor, a2: torch.Te
     """y = x @ w^T + a2[:, group block] @ b2^T (+ residual) with both weight orientations at hand (w [N, K], wT [K, N],
     b2 [N, K2], b2T [K2, N]): the NN kernel for chip-filling problems with 256-aligned groups, else the NT kernels."""
     M, N = x.shape[0], w.shape[0]
-    if ((M + 255) // 256) * ((N + 255) // 256) >= 192 and group_cols % 256 == 0 and group0 % 256 == 0 and N % 8 == 0:
+    if _fills_chip(M, N) and group_cols % 256 == 0 and group0 % 256 == 0 and N % 8 == 0:
         K, K2 = x.shape[1], b2T.shape[0]
         # (adapter-first instead of in-ring: measured equal in time - 918.0 vs 917.9 ms per config-5 step - so the in-ring form,
         #  whose summation order the committed LoRA fixtures were checked with, stays the default: profiles/r04_lora_fwd_pre_ab.log)
@@ -203,11 +209,9 @@ def gemm_nt_dropout(a: torch.Tensor, b: torch.Tensor, p: float, seed: int, out: 
     _chk2d(a, "a"), _chk2d(b, "b")
     M, K = a.shape
     N = b.shape[0]
-    if out is None:
-        out = torch.empty(M, N, dtype=BF16, device=a.device)
-    _chk2d(out, "out")
-    hip.call("rv_gemm_nt_dropout_bf16", a, a.stride(0), b, b.stride(0), out, out.stride(0), M, N, K, residual,
-             residual.stride(0) if residual is not None else 0, float(alpha), float(p), int(seed) & 0x7FFFFFFF)
+    out = _out(out, M, N, a)
+    hip.call("rv_gemm_nt_dropout_bf16", a, a.stride(0), b, b.stride(0), out, out.stride(0), M, N, K, residual, _ld(residual),
+             float(alpha), float(p), _seed31(seed))
     return out
 
 
@@ -222,7 +226,7 @@ def lora_dgrad_dropout(dy: torch.Tensor, w: torch.Tensor, wT: torch.Tensor, dt: 
     K2, N = a.shape
     if w.shape[0] != K or w.shape[1] < N or dt.shape != (M, K2):
         raise ValueError(f"lora_dgrad_dropout: shape mismatch dy{tuple(dy.shape)} w{tuple(w.shape)} dt{tuple(dt.shape)} a{tuple(a.shape)}")
-    if (K % 64 == 0 and K >= 512 and K2 % 64 == 0 and N % 8 == 0 and ((M + 255) // 256) * ((N + 255) // 256) >= 192
+    if (K % 64 == 0 and K >= 512 and K2 % 64 == 0 and N % 8 == 0 and _fills_chip(M, N)
             and os.environ.get("RV_LORA_DGRAD_PRE", "1") != "0"):
         return gemm_nn_lora_pre(dy, w[:, :N], dt, a, p, seed)
     dx = linear(dy, wT, w)
@@ -241,12 +245,9 @@ def gemm_nn_lora_pre(a: torch.Tensor, b: torch.Tensor, a2: torch.Tensor, b2: tor
     groups = _lora_groups(N, group_cols, group0)
     if b.shape != (K, N) or a2.shape != (M, groups * K2):
         raise ValueError(f"gemm_nn_lora_pre: shape mismatch a{tuple(a.shape)} b{tuple(b.shape)} a2{tuple(a2.shape)} b2{tuple(b2.shape)}")
-    if out is None:
-        out = torch.empty(M, N, dtype=BF16, device=a.device)
-    _chk2d(out, "out")
+    out = _out(out, M, N, a)
     hip.call("rv_gemm_nn_lora_pre_bf16", a, a.stride(0), b, b.stride(0), a2, a2.stride(0), b2, b2.stride(0), K2, int(group_cols),
-             int(group0), float(p), int(seed) & 0x7FFFFFFF, out, out.stride(0), M, N, K, residual,
-             residual.stride(0) if residual is not None else 0)
+             int(group0), float(p), _seed31(seed), out, out.stride(0), M, N, K, residual, _ld(residual))
     return out
 
 
@@ -276,9 +277,7 @@ def gemm_tn_skinny(p: torch.Tensor, q: torch.Tensor, out: Optional[torch.Tensor]
     Rq, J = q.shape
     if R != Rq:
         raise ValueError(f"gemm_tn_skinny: row mismatch {R} vs {Rq}")
-    if out is None:
-        out = torch.empty(I, J, dtype=BF16, device=p.device)
-    _chk2d(out, "out")
+    out = _out(out, I, J, p)
     if splits <= 0:
         splits = _splitk_plan(R, I, J)
     hip.call("rv_gemm_tn_bf16_splitk", p, p.stride(0), q, q.stride(0), out, out.stride(0), R, I, J, float(alpha),
@@ -288,7 +287,7 @@ def gemm_tn_skinny(p: torch.Tensor, q: torch.Tensor, out: Optional[torch.Tensor]
 
 # ---- LoRA adapter dropout with one mask per peft module (RV_LORA_PEFT_MASKS): the masks are drawn inside the adapter kernels
 def _module_seeds(seeds, who: str) -> Tuple[int, int, int]:
-    seeds = [int(s) & 0x7FFFFFFF for s in seeds]
+    seeds = [_seed31(s) for s in seeds]
     if not 1 <= len(seeds) <= 3:
         raise ValueError(f"{who}: 1 to 3 module seeds, got {len(seeds)}")
     return tuple(seeds + [0] * (3 - len(seeds)))
@@ -309,9 +308,7 @@ def lora_down_module_masks(x: torch.Tensor, a: torch.Tensor, p: float, seeds, al
     s = _module_seeds(seeds, "lora_down_module_masks")
     if a.shape != (64 * G, K):
         raise ValueError(f"lora_down_module_masks: a must be [{64 * G}, {K}] for {G} modules, got {tuple(a.shape)}")
-    if out is None:
-        out = torch.empty(M, 64 * G, dtype=BF16, device=x.device)
-    _chk2d(out, "out")
+    out = _out(out, M, 64 * G, x)
     if out.shape != (M, 64 * G):
         raise ValueError(f"lora_down_module_masks: out must be [{M}, {64 * G}], got {tuple(out.shape)}")
     hip.call("rv_gemm_nt_lora_masks_bf16", x, x.stride(0), a, a.stride(0), out, out.stride(0), M, K, G, float(alpha), float(p), *s)
@@ -328,15 +325,13 @@ def lora_dgrad_module_masks(dt: torch.Tensor, aT: torch.Tensor, p: float, seeds,
     s = _module_seeds(seeds, "lora_dgrad_module_masks")
     if dt.shape[1] != 64 * G or aT.shape[1] != 64 * G:
         raise ValueError(f"lora_dgrad_module_masks: dt / aT must have {64 * G} columns for {G} modules, got {tuple(dt.shape)} {tuple(aT.shape)}")
-    if out is None:
-        out = torch.empty(M, N, dtype=BF16, device=dt.device)
-    _chk2d(out, "out")
+    out = _out(out, M, N, dt)
     if residual is not None:
         _chk2d(residual, "residual")
     if out.shape != (M, N) or (residual is not None and residual.shape != (M, N)):
         raise ValueError(f"lora_dgrad_module_masks: out / residual must be [{M}, {N}]")
-    hip.call("rv_gemm_nt_dropout_masks_bf16", dt, dt.stride(0), aT, aT.stride(0), out, out.stride(0), M, N, G, residual,
-             residual.stride(0) if residual is not None else 0, float(p), *s)
+    hip.call("rv_gemm_nt_dropout_masks_bf16", dt, dt.stride(0), aT, aT.stride(0), out, out.stride(0), M, N, G, residual, _ld(residual),
+             float(p), *s)
     return out
 
 
@@ -350,9 +345,7 @@ def lora_wgrad_module_masks(dt: torch.Tensor, x: torch.Tensor, p: float, seeds, 
     s = _module_seeds(seeds, "lora_wgrad_module_masks")
     if dt.shape != (R, 64 * G):
         raise ValueError(f"lora_wgrad_module_masks: dt must be [{R}, {64 * G}] for {G} modules, got {tuple(dt.shape)}")
-    if out is None:
-        out = torch.empty(64 * G, K, dtype=BF16, device=x.device)
-    _chk2d(out, "out")
+    out = _out(out, 64 * G, K, x)
     if out.shape != (64 * G, K):
         raise ValueError(f"lora_wgrad_module_masks: out must be [{64 * G}, {K}], got {tuple(out.shape)}")
     if splits <= 0:
@@ -430,7 +423,7 @@ def rmsnorm_fwd_dropout(x, w, eps: float, p: float, seed: int, row_idx: Optional
     outd = torch.empty(rows, d, dtype=BF16, device=x.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if want_rstd else None
     hip.call("rv_rmsnorm_fwd_dropout", x, x.stride(0), row_idx, w, out, out.stride(0), rstd, rows, d, float(eps), outd, float(p),
-             int(seed) & 0x7FFFFFFF)
+             _seed31(seed))
     return out, rstd, outd
 
 
@@ -544,7 +537,7 @@ def swiglu_fwd_dropout(gu: torch.Tensor, p: float, seed: int):
     f = f2 // 2
     out = torch.empty(rows, f, dtype=BF16, device=gu.device)
     outd = torch.empty(rows, f, dtype=BF16, device=gu.device)
-    hip.call("rv_swiglu_fwd_dropout", gu, gu.stride(0), out, out.stride(0), rows, f, outd, float(p), int(seed) & 0x7FFFFFFF)
+    hip.call("rv_swiglu_fwd_dropout", gu, gu.stride(0), out, out.stride(0), rows, f, outd, float(p), _seed31(seed))
     return out, outd
 
 
@@ -584,13 +577,13 @@ def linear_lora_swiglu(x: torch.Tensor, wguT: torch.Tensor, t: torch.Tensor, bex
     act = torch.empty(M, N // 2, dtype=BF16, device=x.device)
     actd = torch.empty_like(act) if p > 0.0 else None
     hip.call("rv_gemm_nn_lora_swiglu_bf16", x, x.stride(0), wguT, wguT.stride(0), t, t.stride(0), bexp, bexp.stride(0), K2,
-             gu, gu.stride(0), act, act.stride(0), actd, float(p), int(seed) & 0x7FFFFFFF, M, N, K)
+             gu, gu.stride(0), act, act.stride(0), actd, float(p), _seed31(seed), M, N, K)
     return gu, act, actd
 
 
 def linear_lora_swiglu_ok(M: int, f: int, d: int, r_pad: int) -> bool:
     """Whether the fused adapter SwiGLU GEMMs serve this shape (chip-filling, 64-deep-A kernel)."""
-    return d % 64 == 0 and d >= 512 and r_pad % 64 == 0 and f % 8 == 0 and ((M + 255) // 256) * ((2 * f + 255) // 256) >= 192
+    return d % 64 == 0 and d >= 512 and r_pad % 64 == 0 and f % 8 == 0 and _fills_chip(M, 2 * f)
 
 
 def linear_lora_swiglu_bwd(dy: torch.Tensor, w_down: torch.Tensor, dt: torch.Tensor, a_down: torch.Tensor, gu: torch.Tensor,
@@ -605,7 +598,7 @@ def linear_lora_swiglu_bwd(dy: torch.Tensor, w_down: torch.Tensor, dt: torch.Ten
         raise ValueError("linear_lora_swiglu_bwd: shapes")
     dgu = torch.empty_like(gu)
     hip.call("rv_gemm_nn_lora_swiglu_bwd_bf16", dy, dy.stride(0), w_down, w_down.stride(0), dt, dt.stride(0), a_down, a_down.stride(0),
-             K2, float(p), int(seed) & 0x7FFFFFFF, gu, gu.stride(0), dgu, dgu.stride(0), M, f, K)
+             K2, float(p), _seed31(seed), gu, gu.stride(0), dgu, dgu.stride(0), M, f, K)
     return dgu
 
 
@@ -639,7 +632,7 @@ def dropout(x: torch.Tensor, p: float, seed: int, out=_NO_OUT, accumulate_into: 
         raise ValueError("dropout: contiguous tensors required")
     if out is _NO_OUT:
         out = torch.empty_like(x)
-    hip.call("rv_dropout", x, out, accumulate_into, x.numel(), float(p), int(seed) & 0x7FFFFFFF)
+    hip.call("rv_dropout", x, out, accumulate_into, x.numel(), float(p), _seed31(seed))
     return out if out is not None else accumulate_into
 
 
@@ -872,7 +865,7 @@ def sample_token(logits: torch.Tensor, n_rows: int, v_valid: int, u: Optional[to
 def gemm_auto_variant(M: int, N: int) -> int:
     """The NT GEMM kernel the library picks for an [M, N] output when no variant is forced (gemm.hip dispatch: the 256 x 256
     tile kernel from 192 tiles on)."""
-    return 3 if ((M + 255) // 256) * ((N + 255) // 256) >= 192 else 1
+    return 3 if _fills_chip(M, N) else 1
 
 
 def lmhead_logp_unpack(h: torch.Tensor, w: torch.Tensor, tgt: torch.Tensor, n_rows: int, dst_a: torch.Tensor,

@@ -751,10 +751,12 @@ def c_gemm_nt_lora(dev, shape, residual):
     chk(c, acc + res.double() if residual else acc, f"rv_gemm_nt_lora_bf16 C ({shape}, residual = {residual})")
 
 
-@case(*grid(kind=["nn_lora", "pre p=0", "pre p=0.3"]))
+@case(*grid(kind=["nn_lora", "nn_lora a64 mi16=0", "pre p=0", "pre p=0.3"]))
 def c_gemm_nn_lora(dev, kind):
-    """rv_gemm_nn_lora_bf16 (K = 128) and rv_gemm_nn_lora_pre_bf16 (K >= 512 is its documented minimum: A sparse, see _sparse):
-    pre with p > 0 masks the adapter segment's fp32 accumulators (times inv_keep), the main segment accumulates on top - one rounding"""
+    """rv_gemm_nn_lora_bf16 (K = 128: the 32-deep kernel; K = 512 with rv_set_gemm_mi16(0): the 64-deep-A kernel's 32x32x16 loop with
+    the second K segment, which no other test reaches) and rv_gemm_nn_lora_pre_bf16 (K >= 512 is its documented minimum: A sparse, see
+    _sparse): pre with p > 0 masks the adapter segment's fp32 accumulators (times inv_keep), the main segment accumulates on top - one
+    rounding"""
     from rlaif_v_amd import ops
     M, N, K2, gc = 300, 512, 64, 256
     K = 128 if kind == "nn_lora" else 512
@@ -766,6 +768,11 @@ def c_gemm_nn_lora(dev, kind):
         chk(c, _lora_acc(a, b, a2, b2, gc, dev) + res.double(), "rv_gemm_nn_lora_bf16 C")
         return
     a = _sparse(a)
+    if kind.startswith("nn_lora"):
+        call("rv_set_gemm_mi16", 0)
+        c = ops.gemm_nn_lora(a, b, a2, b2, group_cols=gc, residual=res)
+        chk(c, _lora_acc(a, b, a2, b2, gc, dev) + res.double(), "rv_gemm_nn_lora_bf16 C (K = 512, mi16 = 0)")
+        return
     p, seed = (0.3, 4711) if kind.endswith("0.3") else (0.0, 0)
     c = ops.gemm_nn_lora_pre(a, b, a2, b2, p=p, seed=seed, group_cols=gc, residual=res)
     if p == 0.0:
