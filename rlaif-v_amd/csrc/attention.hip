@@ -10,9 +10,9 @@
 //  * K/V (or Q/dO) tiles are double-buffered in LDS by global_load_lds; XOR chunk swizzles keep both the
 //    32-row ds_read_b128 pattern and the 4-row transposing reads bank-conflict free.
 #include "common.hpp"
+#include "host.hpp"
 #include "rlaifv_hip.h"
 
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -1429,8 +1429,77 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv5_kernel(const bf16_t* __r
 
 }  // namespace
 
+// Instantiates the kernels in the order they have always had in .text, whatever order the launches below name them in: the
+// listings of tools/kernel_resources.py follow it, and they are compared line by line from one change to the next.
+[[maybe_unused]] static const void* const kernels_in_text_order[] = {
+    (const void*)attn_fwd3_kernel<true>,           (const void*)attn_fwd3_kernel<false>,
+    (const void*)attn_fwd2_kernel<128, true>,      (const void*)attn_fwd2_kernel<128, false>,
+    (const void*)attn_fwd2_kernel<128, true, 8>,   (const void*)attn_fwd2_kernel<128, false, 8>,
+    (const void*)attn_fwd2_kernel<64, true>,       (const void*)attn_fwd2_kernel<64, false>,
+    (const void*)attn_fwd2_kernel<128, true, 4, true>, (const void*)attn_fwd2_kernel<64, true, 4, true>,
+    (const void*)attn_bwd_dq2_kernel<true>,        (const void*)attn_bwd_dq2_kernel<false>,
+    (const void*)attn_bwd_dkv3_kernel<true>,       (const void*)attn_bwd_dkv3_kernel<false>,
+    (const void*)attn_bwd_dkv5_kernel<true>,       (const void*)attn_bwd_dkv5_kernel<false>};
+
 static int g_dkv_override = 0;
 static int g_fwd_override = 0;
+
+// ---- A/B knobs of the environment, one accessor each ----
+// RV_ATTN_MAP: how the blocks of an (s, h) are spread over the XCDs (bits 16.. of nx)
+static int attn_map() {
+  static const int v = env_int("RV_ATTN_MAP", 1);
+  return v;
+}
+// RV_ATTN_PAIR: 0 = the plain (x, n-1-x) pairing, 1 = pair_blocks (ranked pairs), 2 = one ranked block per workgroup
+static int attn_pair() {
+  static const int v = env_int("RV_ATTN_PAIR", 1);
+  return v;
+}
+// RV_ATTN_FWD_NW: 4 = 128-query workgroups (two per CU), 8 = 256-query workgroups on one K / V ring (hd 128)
+static int attn_fwd_nw() {
+  static const int v = env_int("RV_ATTN_FWD_NW", 4) == 8 ? 8 : 4;
+  return v;
+}
+// RV_ATTN_FWD: 3 = attn_fwd3_kernel (hd 128; csrc/attn_fwd3.inc), 2 = attn_fwd2_kernel (default); rv_set_attn_fwd_version goes first
+static int attn_fwd_version() {
+  static const int v = env_int("RV_ATTN_FWD", 2) == 3 ? 3 : 2;
+  return g_fwd_override ? g_fwd_override : v;
+}
+// RV_ATTN_DKV: 3 = the round-2/3 kernel, 5 = the round-4 kernel (tools/gen_attn_dkv5.py, default; versions 2 and 4: history);
+// rv_set_attn_dkv_version goes first (tests: both kernels in one process)
+static int attn_dkv_version() {
+  static const int v = env_int("RV_ATTN_DKV", 5) == 3 ? 3 : 5;
+  return g_dkv_override ? g_dkv_override : v;
+}
+
+// Workgroups per (s, h) and the kernels' packed `nx` argument (nxr | map << 16 | ranked pairs << 20 | ranked singles << 21) for
+// sequences of L tokens in blocks of q_block queries: a causal workgroup takes a pair of blocks unless pair == 2.
+struct AttnGrid { int nxr, nx; };
+static AttnGrid attn_grid(int L, int q_block, bool causal, int map, int pair) {
+  const int nb = (L + q_block - 1) / q_block;
+  const int nxr = (causal && pair != 2) ? (nb + 1) / 2 : nb;
+  return AttnGrid{nxr, nxr | (map << 16) | ((pair ? 1 : 0) << 20) | ((causal && pair == 2 ? 1 : 0) << 21)};
+}
+
+// what rv_attn_fwd and rv_attn_fwd_branches ask of their operands
+static int check_attn_io(const char* who, int hd, const int* row_off, const int* row_len, int H, int kv_group, long ld, long ldo,
+                         int q_col0, int k_col0, int v_col0, int L) {
+  RV_REQUIRE_AS(who, hd == 64 || hd == 128, "head dim must be 64 or 128");
+  RV_REQUIRE_AS(who, (row_off == nullptr) == (row_len == nullptr), "row_off and row_len go together");
+  RV_REQUIRE_AS(who, kv_group >= 1 && H % kv_group == 0, "kv_group must divide the number of query heads");
+  RV_REQUIRE_AS(who, ld % 8 == 0 && ldo % 8 == 0 && q_col0 % 8 == 0 && k_col0 % 8 == 0 && v_col0 % 8 == 0, "alignment");
+  RV_REQUIRE_AS(who, (double)L * (double)ld * 2.0 < 4.0e9, "one sequence must span < 4 GB of the qkv buffer (32-bit DMA offsets)");
+  return 0;
+}
+
+// f(std::bool_constant<causal>{}): the kernels take `causal` as a template argument
+template <class F>
+static int for_causal(int causal, F&& f) {
+  return causal ? f(std::true_type{}) : f(std::false_type{});
+}
+// a kernel as a value, so that one generic lambda can hold the argument list that several instantiations share
+template <auto Kernel>
+using kernel_c = std::integral_constant<decltype(Kernel), Kernel>;
 
 extern "C" {
 
@@ -1451,101 +1520,39 @@ long rv_attn_bwd_workspace_floats(int S, int H, int L) { return 3L * S * H * L; 
 int rv_attn_fwd(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, void* out, long ldo, float* lse, int S,
                 int L, int H, int hd, int causal, float scale, const int* seg_sh, const int* seg_e1, int kv_group,
                 const int* row_off, const int* row_len, void* stream) {
-  RV_REQUIRE(hd == 64 || hd == 128, "rv_attn_fwd: head dim must be 64 or 128");
-  RV_REQUIRE((row_off == nullptr) == (row_len == nullptr), "rv_attn_fwd: row_off and row_len go together");
-  RV_REQUIRE(kv_group >= 1 && H % kv_group == 0, "rv_attn_fwd: kv_group must divide the number of query heads");
-  RV_REQUIRE(ld % 8 == 0 && ldo % 8 == 0 && q_col0 % 8 == 0 && k_col0 % 8 == 0 && v_col0 % 8 == 0,
-             "rv_attn_fwd: alignment");
-  RV_REQUIRE((double)L * (double)ld * 2.0 < 4.0e9, "rv_attn_fwd: one sequence must span < 4 GB of the qkv buffer (32-bit DMA offsets)");
+  if (check_attn_io(__func__, hd, row_off, row_len, H, kv_group, ld, ldo, q_col0, k_col0, v_col0, L)) return 1;
   if (S == 0 || L == 0) return 0;
-  static int map_mode = -1;
-  if (map_mode < 0) { const char* e = getenv("RV_ATTN_MAP"); map_mode = e ? atoi(e) : 1; }
-  hipStream_t st = (hipStream_t)stream;
-  static int fwd_nw = -1;         // RV_ATTN_FWD_NW: 4 = 128-query workgroups (two per CU), 8 = 256-query workgroups on one K / V ring (hd 128)
-  if (fwd_nw < 0) { const char* e = getenv("RV_ATTN_FWD_NW"); fwd_nw = (e && atoi(e) == 8) ? 8 : 4; }
-  static int fwd_env = -1;        // RV_ATTN_FWD: 3 = attn_fwd3_kernel (hd 128; csrc/attn_fwd3.inc), 2 = attn_fwd2_kernel (default)
-  if (fwd_env < 0) { const char* e = getenv("RV_ATTN_FWD"); fwd_env = (e && (atoi(e) == 2 || atoi(e) == 3)) ? atoi(e) : 2; }
-  const int fwd_ver = g_fwd_override ? g_fwd_override : fwd_env;
-  const bool v3 = hd == 128 && fwd_ver == 3;
-  const int nw = v3 ? 8 : (hd == 128) ? fwd_nw : 4;             // version 3: 256-query blocks (4 waves x 64 rows)
-  const int nb = (L + 32 * nw - 1) / (32 * nw);
-  static int pair_mode = -1;      // RV_ATTN_PAIR: 0 = the plain (x, n-1-x) pairing, 1 = pair_blocks (ranked pairs), 2 = one ranked block per workgroup
-  if (pair_mode < 0) { const char* e = getenv("RV_ATTN_PAIR"); pair_mode = e ? atoi(e) : 1; }
-  const int nxr = (causal && pair_mode != 2) ? (nb + 1) / 2 : nb;
-  const int nx = nxr | (map_mode << 16) | ((pair_mode ? 1 : 0) << 20) | ((causal && pair_mode == 2 ? 1 : 0) << 21);
-  dim3 grid(nxr * H * S), block(64 * nw);
-  static bool attr_done = false;
-  if (v3) {
-    static bool attr3_done = false;
-    if (!attr3_done) {
-      hipFuncSetAttribute((const void*)attn_fwd3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 7 * 64 * 128 * 2);
-      hipFuncSetAttribute((const void*)attn_fwd3_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 7 * 64 * 128 * 2);
-      attr3_done = true;
-    }
-    if (causal)
-      hipLaunchKernelGGL((attn_fwd3_kernel<true>), grid, dim3(256), 7 * 64 * 128 * 2, st, (const bf16_t*)qkv, ld, q_col0, k_col0, v_col0,
-                         (bf16_t*)out, ldo, lse, L, H, nx, scale, seg_sh, seg_e1, kv_group, row_off, row_len);
-    else
-      hipLaunchKernelGGL((attn_fwd3_kernel<false>), grid, dim3(256), 7 * 64 * 128 * 2, st, (const bf16_t*)qkv, ld, q_col0, k_col0, v_col0,
-                         (bf16_t*)out, ldo, lse, L, H, nx, scale, seg_sh, seg_e1, kv_group, row_off, row_len);
-    RV_CHECK_LAUNCH();
-    return 0;
-  }
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)attn_fwd2_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    hipFuncSetAttribute((const void*)attn_fwd2_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    hipFuncSetAttribute((const void*)attn_fwd2_kernel<128, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    hipFuncSetAttribute((const void*)attn_fwd2_kernel<128, false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-    attr_done = true;
-  }
-#define LAUNCH_FWD(HD_, C_)                                                                                      \
-  hipLaunchKernelGGL((attn_fwd2_kernel<HD_, C_>), grid, block, 4 * 64 * HD_ * 2, st, (const bf16_t*)qkv, ld, q_col0, \
-                     k_col0, v_col0, (bf16_t*)out, ldo, lse, L, H, nx, scale, seg_sh, seg_e1, kv_group, row_off, row_len)
-  if (hd == 128 && nw == 8) {
-    if (causal)
-      hipLaunchKernelGGL((attn_fwd2_kernel<128, true, 8>), grid, block, 4 * 64 * 128 * 2, st, (const bf16_t*)qkv, ld, q_col0, k_col0,
-                         v_col0, (bf16_t*)out, ldo, lse, L, H, nx, scale, seg_sh, seg_e1, kv_group, row_off, row_len);
-    else
-      hipLaunchKernelGGL((attn_fwd2_kernel<128, false, 8>), grid, block, 4 * 64 * 128 * 2, st, (const bf16_t*)qkv, ld, q_col0, k_col0,
-                         v_col0, (bf16_t*)out, ldo, lse, L, H, nx, scale, seg_sh, seg_e1, kv_group, row_off, row_len);
-  } else if (hd == 128) { if (causal) LAUNCH_FWD(128, true); else LAUNCH_FWD(128, false); }
-  else { if (causal) LAUNCH_FWD(64, true); else LAUNCH_FWD(64, false); }
-#undef LAUNCH_FWD
-  RV_CHECK_LAUNCH();
-  return 0;
+  const bool v3 = hd == 128 && attn_fwd_version() == 3;
+  const int nw = v3 ? 8 : (hd == 128) ? attn_fwd_nw() : 4;      // version 3: 256-query blocks (4 waves x 64 rows)
+  const AttnGrid g = attn_grid(L, 32 * nw, causal, attn_map(), attn_pair());
+  const dim3 grid(g.nxr * H * S);
+  return for_causal(causal, [&](auto C) {
+    constexpr bool C_ = decltype(C)::value;
+    const auto fwd = [&](auto kernel, int threads, int lds) {
+      return launch<decltype(kernel)::value>(lds, grid, dim3(threads), stream, (const bf16_t*)qkv, ld, q_col0, k_col0, v_col0, (bf16_t*)out,
+                                             ldo, lse, L, H, g.nx, scale, seg_sh, seg_e1, kv_group, row_off, row_len);
+    };
+    if (v3) return fwd(kernel_c<attn_fwd3_kernel<C_>>{}, 256, 7 * 64 * 128 * 2);
+    if (hd == 128 && nw == 8) return fwd(kernel_c<attn_fwd2_kernel<128, C_, 8>>{}, 512, 4 * 64 * 128 * 2);
+    if (hd == 128) return fwd(kernel_c<attn_fwd2_kernel<128, C_>>{}, 256, 4 * 64 * 128 * 2);
+    return fwd(kernel_c<attn_fwd2_kernel<64, C_>>{}, 256, 4 * 64 * 64 * 2);
+  });
 }
 
 int rv_attn_fwd_branches(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, void* out, long ldo, float* lse, int S,
                          int L, int H, int hd, float scale, const int* seg_sh, const int* q_lo, int kv_group, const int* row_off,
                          const int* row_len, void* stream) {
-  RV_REQUIRE(hd == 64 || hd == 128, "rv_attn_fwd_branches: head dim must be 64 or 128");
   RV_REQUIRE(seg_sh != nullptr && q_lo != nullptr, "rv_attn_fwd_branches: seg_sh and q_lo are required");
-  RV_REQUIRE((row_off == nullptr) == (row_len == nullptr), "rv_attn_fwd_branches: row_off and row_len go together");
-  RV_REQUIRE(kv_group >= 1 && H % kv_group == 0, "rv_attn_fwd_branches: kv_group must divide the number of query heads");
-  RV_REQUIRE(ld % 8 == 0 && ldo % 8 == 0 && q_col0 % 8 == 0 && k_col0 % 8 == 0 && v_col0 % 8 == 0,
-             "rv_attn_fwd_branches: alignment");
-  RV_REQUIRE((double)L * (double)ld * 2.0 < 4.0e9,
-             "rv_attn_fwd_branches: one sequence must span < 4 GB of the qkv buffer (32-bit DMA offsets)");
+  if (check_attn_io(__func__, hd, row_off, row_len, H, kv_group, ld, ldo, q_col0, k_col0, v_col0, L)) return 1;
   if (S == 0 || L == 0) return 0;
-  // 128-query workgroups, the nx blocks of an (s, h) on one XCD, ranked block pairs: rv_attn_fwd's defaults
-  const int nb = (L + 127) / 128, nxr = (nb + 1) / 2;
-  const int nx = nxr | (1 << 16) | (1 << 20);
-  dim3 grid(nxr * H * S), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (hd == 128) {
-    static bool attr_done = false;
-    if (!attr_done) {
-      hipFuncSetAttribute((const void*)attn_fwd2_kernel<128, true, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-      attr_done = true;
-    }
-    hipLaunchKernelGGL((attn_fwd2_kernel<128, true, 4, true>), grid, block, 4 * 64 * 128 * 2, st, (const bf16_t*)qkv, ld, q_col0, k_col0,
-                       v_col0, (bf16_t*)out, ldo, lse, L, H, nx, scale, seg_sh, q_lo, kv_group, row_off, row_len);
-  } else {
-    hipLaunchKernelGGL((attn_fwd2_kernel<64, true, 4, true>), grid, block, 4 * 64 * 64 * 2, st, (const bf16_t*)qkv, ld, q_col0, k_col0,
-                       v_col0, (bf16_t*)out, ldo, lse, L, H, nx, scale, seg_sh, q_lo, kv_group, row_off, row_len);
-  }
-  RV_CHECK_LAUNCH();
-  return 0;
+  // 128-query workgroups, the nx blocks of an (s, h) on one XCD, ranked block pairs: rv_attn_fwd's defaults, whatever the environment says
+  const AttnGrid g = attn_grid(L, 128, true, 1, 1);
+  const auto fwd = [&](auto kernel, int lds) {
+    return launch<decltype(kernel)::value>(lds, dim3(g.nxr * H * S), dim3(256), stream, (const bf16_t*)qkv, ld, q_col0, k_col0, v_col0,
+                                           (bf16_t*)out, ldo, lse, L, H, g.nx, scale, seg_sh, q_lo, kv_group, row_off, row_len);
+  };
+  if (hd == 128) return fwd(kernel_c<attn_fwd2_kernel<128, true, 4, true>>{}, 4 * 64 * 128 * 2);
+  return fwd(kernel_c<attn_fwd2_kernel<64, true, 4, true>>{}, 4 * 64 * 64 * 2);
 }
 
 int rv_attn_bwd(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, const void* dO, long lddo,
@@ -1564,56 +1571,27 @@ int rv_attn_bwd(const void* qkv, long ld, int q_col0, int k_col0, int v_col0, co
   RV_REQUIRE(ld % 8 == 0 && lddo % 8 == 0 && lddq % 8 == 0, "rv_attn_bwd: alignment");
   RV_REQUIRE((double)L * (double)(ld > lddo ? ld : lddo) * 2.0 < 4.0e9, "rv_attn_bwd: one sequence must span < 4 GB of the qkv / dO buffers");
   if (S == 0 || L == 0) return 0;
-  const int nb = (L + 127) / 128;
-  static int map_mode = -1;
-  if (map_mode < 0) { const char* e = getenv("RV_ATTN_MAP"); map_mode = e ? atoi(e) : 1; }
-  static int pair_mode = -1;
-  if (pair_mode < 0) { const char* e = getenv("RV_ATTN_PAIR"); pair_mode = e ? atoi(e) : 1; }
-  const int nxr = (causal && pair_mode != 2) ? (nb + 1) / 2 : nb;
-  const int nx = nxr | (map_mode << 16) | ((pair_mode ? 1 : 0) << 20) | ((causal && pair_mode == 2 ? 1 : 0) << 21);
-  dim3 grid(nxr * H * S), block(256);
-  hipStream_t st = (hipStream_t)stream;
+  const AttnGrid g = attn_grid(L, 128, causal, attn_map(), attn_pair());
   constexpr int DQ_LDS = 4 * 64 * 256;
   constexpr int DKV_LDS = 2 * (2 * 64 * 256 + 512);
   constexpr int DKV5_LDS = 4 * (2 * 64 * 256 + 512);     // version 5: four-stage ring
-  static bool attr_done = false;
-  static int dkv_env = 5;            // round 4: version 5 (tools/gen_attn_dkv5.py); RV_ATTN_DKV=3 selects the round-2/3 kernel
-  if (!attr_done) {
-    hipFuncSetAttribute((const void*)attn_bwd_dq2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ_LDS);
-    hipFuncSetAttribute((const void*)attn_bwd_dq2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, DQ_LDS);
-    hipFuncSetAttribute((const void*)attn_bwd_dkv3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS);
-    hipFuncSetAttribute((const void*)attn_bwd_dkv3_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV_LDS);
-    hipFuncSetAttribute((const void*)attn_bwd_dkv5_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV5_LDS);
-    hipFuncSetAttribute((const void*)attn_bwd_dkv5_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, DKV5_LDS);
-    const char* e = getenv("RV_ATTN_DKV");        // A/B knob: 3 = the round-2/3 kernel, 5 = the round-4 kernel (versions 2 and 4: history)
-    if (e && (atoi(e) == 3 || atoi(e) == 5)) dkv_env = atoi(e);
-    attr_done = true;
-  }
-  const int dkv_version = g_dkv_override ? g_dkv_override : dkv_env;      // rv_set_attn_dkv_version (tests: both kernels in one process)
   // dQ: one workgroup per (query head, query block); dK/dV: per (KEY/VALUE head, key block), looping over its query heads
   const int Hkv = H / kv_group;
-  dim3 grid_kv(nxr * Hkv * S);
-#define BWD_HEAD (const bf16_t*)qkv, ld, q_col0, k_col0, v_col0, (const bf16_t*)dO, lddo
-#define BWD_TAIL(HH) (bf16_t*)dqkv, lddq, L, HH, nx, scale, seg_sh, seg_e1, kv_group, rope_cos, rope_sin, rope_pos, row_off, row_len
-  if (causal) {
-    hipLaunchKernelGGL((attn_bwd_dq2_kernel<true>), grid, block, DQ_LDS, st, BWD_HEAD, (const bf16_t*)O, ldo, lse, delta, BWD_TAIL(H));
-    RV_CHECK_LAUNCH();
-    if (dkv_version == 5)
-      hipLaunchKernelGGL((attn_bwd_dkv5_kernel<true>), grid_kv, block, DKV5_LDS, st, BWD_HEAD, lse, (const float*)delta, BWD_TAIL(Hkv));
-    else
-      hipLaunchKernelGGL((attn_bwd_dkv3_kernel<true>), grid_kv, block, DKV_LDS, st, BWD_HEAD, lse, (const float*)delta, BWD_TAIL(Hkv));
-  } else {
-    hipLaunchKernelGGL((attn_bwd_dq2_kernel<false>), grid, block, DQ_LDS, st, BWD_HEAD, (const bf16_t*)O, ldo, lse, delta, BWD_TAIL(H));
-    RV_CHECK_LAUNCH();
-    if (dkv_version == 5)
-      hipLaunchKernelGGL((attn_bwd_dkv5_kernel<false>), grid_kv, block, DKV5_LDS, st, BWD_HEAD, lse, (const float*)delta, BWD_TAIL(Hkv));
-    else
-      hipLaunchKernelGGL((attn_bwd_dkv3_kernel<false>), grid_kv, block, DKV_LDS, st, BWD_HEAD, lse, (const float*)delta, BWD_TAIL(Hkv));
-  }
-#undef BWD_HEAD
-#undef BWD_TAIL
-  RV_CHECK_LAUNCH();
-  return 0;
+  const dim3 grid(g.nxr * H * S), grid_kv(g.nxr * Hkv * S), block(256);
+  return for_causal(causal, [&](auto C) {
+    constexpr bool C_ = decltype(C)::value;
+    const auto dkv = [&](auto kernel, int lds) {
+      return launch<decltype(kernel)::value>(lds, grid_kv, block, stream, (const bf16_t*)qkv, ld, q_col0, k_col0, v_col0, (const bf16_t*)dO,
+                                             lddo, lse, (const float*)delta, (bf16_t*)dqkv, lddq, L, Hkv, g.nx, scale, seg_sh, seg_e1,
+                                             kv_group, rope_cos, rope_sin, rope_pos, row_off, row_len);
+    };
+    if (const int rc = launch<attn_bwd_dq2_kernel<C_>>(DQ_LDS, grid, block, stream, (const bf16_t*)qkv, ld, q_col0, k_col0, v_col0,
+                                                       (const bf16_t*)dO, lddo, (const bf16_t*)O, ldo, lse, delta, (bf16_t*)dqkv, lddq, L, H,
+                                                       g.nx, scale, seg_sh, seg_e1, kv_group, rope_cos, rope_sin, rope_pos, row_off, row_len))
+      return rc;
+    if (attn_dkv_version() == 5) return dkv(kernel_c<attn_bwd_dkv5_kernel<C_>>{}, DKV5_LDS);
+    return dkv(kernel_c<attn_bwd_dkv3_kernel<C_>>{}, DKV_LDS);
+  });
 }
 
 }  // extern "C"

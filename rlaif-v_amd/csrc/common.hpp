@@ -130,21 +130,3 @@ struct DropParams { uint32_t thresh16, key; float inv_keep; };
 inline DropParams drop_params(float p, int seed) {
   return DropParams{(uint32_t)((double)p * 65536.0 + 0.5), (uint32_t)seed * 0x9e3779b9u + 0x85ebca6bu, 1.f / (1.f - p)};
 }
-
-// Error plumbing for the C ABI (no exceptions across the boundary).
-void rv_set_error(const char* msg);
-#define RV_CHECK_LAUNCH()                                   \
-  do {                                                      \
-    hipError_t e__ = hipGetLastError();                     \
-    if (e__ != hipSuccess) {                                \
-      rv_set_error(hipGetErrorString(e__));                 \
-      return 2;                                             \
-    }                                                       \
-  } while (0)
-#define RV_REQUIRE(cond, msg)                               \
-  do {                                                      \
-    if (!(cond)) {                                          \
-      rv_set_error(msg);                                    \
-      return 1;                                             \
-    }                                                       \
-  } while (0)

@@ -4,9 +4,8 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "host.hpp"
 #include "rlaifv_hip.h"
-
-#define STREAM(s) ((hipStream_t)(s))
 
 // ------------------------------------------------------------------ skinny NT GEMM
 // One workgroup owns SK_BN = 16 output columns and all M rows: W rows are the MFMA A operand, the activation rows the B
@@ -115,15 +114,14 @@ __global__ __launch_bounds__(SK_WAVES * 64) void gemm_nt_skinny_kernel(const bf1
 }
 
 template <int MT>
-static void launch_skinny(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const void* R, long ldr, int M,
+static int launch_skinny(const void* A, long lda, const void* W, long ldw, void* C, long ldc, const void* R, long ldr, int M,
                           int N, int K, int out_f32, void* stream) {
   const dim3 grid((N + SK_BN - 1) / SK_BN), block(SK_WAVES * 64);
   if (out_f32)
-    hipLaunchKernelGGL((gemm_nt_skinny_kernel<MT, true>), grid, block, 0, STREAM(stream), (const bf16_t*)A, lda,
-                       (const bf16_t*)W, ldw, C, ldc, (const bf16_t*)R, ldr, M, N, K);
-  else
-    hipLaunchKernelGGL((gemm_nt_skinny_kernel<MT, false>), grid, block, 0, STREAM(stream), (const bf16_t*)A, lda,
-                       (const bf16_t*)W, ldw, C, ldc, (const bf16_t*)R, ldr, M, N, K);
+    return launch<gemm_nt_skinny_kernel<MT, true>>(0, grid, block, stream, (const bf16_t*)A, lda, (const bf16_t*)W, ldw, C, ldc,
+                                                   (const bf16_t*)R, ldr, M, N, K);
+  return launch<gemm_nt_skinny_kernel<MT, false>>(0, grid, block, stream, (const bf16_t*)A, lda, (const bf16_t*)W, ldw, C, ldc,
+                                                  (const bf16_t*)R, ldr, M, N, K);
 }
 
 extern "C" int rv_gemm_nt_skinny_bf16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K,
@@ -140,13 +138,11 @@ extern "C" int rv_gemm_nt_skinny_bf16(const void* A, long lda, const void* W, lo
   RV_REQUIRE(residual == nullptr || (ldr % 4 == 0 && ldr >= N && ((uintptr_t)residual & 7) == 0),
              "rv_gemm_nt_skinny_bf16: residual: ldr a multiple of 4, >= N, 8-byte aligned");
   switch ((M + 15) / 16) {
-    case 1: launch_skinny<1>(A, lda, W, ldw, C, ldc, residual, ldr, M, N, K, out_f32, stream); break;
-    case 2: launch_skinny<2>(A, lda, W, ldw, C, ldc, residual, ldr, M, N, K, out_f32, stream); break;
-    case 3: launch_skinny<3>(A, lda, W, ldw, C, ldc, residual, ldr, M, N, K, out_f32, stream); break;
-    default: launch_skinny<4>(A, lda, W, ldw, C, ldc, residual, ldr, M, N, K, out_f32, stream); break;
+    case 1: return launch_skinny<1>(A, lda, W, ldw, C, ldc, residual, ldr, M, N, K, out_f32, stream);
+    case 2: return launch_skinny<2>(A, lda, W, ldw, C, ldc, residual, ldr, M, N, K, out_f32, stream);
+    case 3: return launch_skinny<3>(A, lda, W, ldw, C, ldc, residual, ldr, M, N, K, out_f32, stream);
+    default: return launch_skinny<4>(A, lda, W, ldw, C, ldc, residual, ldr, M, N, K, out_f32, stream);
   }
-  RV_CHECK_LAUNCH();
-  return 0;
 }
 
 // ------------------------------------------------------------------ decode attention
@@ -315,21 +311,19 @@ extern "C" int rv_attn_decode(const void* q, long ldq, const void* kv, long ldkv
   const int nkv = H / kv_group;
   const dim3 grid(nkv * n_split, M), block(256);
   const float sl2 = scale * 1.4426950408889634f;
-#define AD_LAUNCH(G)                                                                                                      \
-  hipLaunchKernelGGL((attn_decode_kernel<G>), grid, block, 0, STREAM(stream), (const bf16_t*)q, ldq, (const bf16_t*)kv, \
-                     ldkv, k_col0, v_col0, pre_off, pre_len, own_off, own_len, H, n_split, sl2, workspace)
+#define AD_LAUNCH(G)                                                                                               \
+  launch<attn_decode_kernel<G>>(0, grid, block, stream, (const bf16_t*)q, ldq, (const bf16_t*)kv, ldkv, k_col0, v_col0, \
+                                pre_off, pre_len, own_off, own_len, H, n_split, sl2, workspace)
+  int rc;
   switch (kv_group) {
-    case 1: AD_LAUNCH(1); break;
-    case 2: AD_LAUNCH(2); break;
-    case 4: AD_LAUNCH(4); break;
-    default: AD_LAUNCH(8); break;
+    case 1: rc = AD_LAUNCH(1); break;
+    case 2: rc = AD_LAUNCH(2); break;
+    case 4: rc = AD_LAUNCH(4); break;
+    default: rc = AD_LAUNCH(8); break;
   }
 #undef AD_LAUNCH
-  RV_CHECK_LAUNCH();
-  hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(H, M), dim3(AD_HD), 0, STREAM(stream), workspace, n_split, (bf16_t*)out,
-                     ldo, lse, H);
-  RV_CHECK_LAUNCH();
-  return 0;
+  if (rc) return rc;
+  return launch<attn_decode_combine_kernel>(0, dim3(H, M), dim3(AD_HD), stream, workspace, n_split, (bf16_t*)out, ldo, lse, H);
 }
 
 // ------------------------------------------------------------------ sampler
@@ -492,15 +486,13 @@ extern "C" int rv_sample_token(const float* logits, long ldl, int M, int V_valid
   RV_REQUIRE(temperature == 0.f || u != nullptr, "rv_sample_token: sampling needs the uniforms u[M]");
   RV_REQUIRE(seen_off == nullptr || seen_ids != nullptr, "rv_sample_token: seen_off without seen_ids");
   const bool pen = seen_off != nullptr && penalty != 1.0f;
-  const size_t lds = pen ? (size_t)((V_valid + 31) / 32) * 4 : 0;
+  const int lds = pen ? (V_valid + 31) / 32 * 4 : 0;
   const int vec = (((uintptr_t)logits & 15) == 0 && ldl % 4 == 0) ? 1 : 0;
-#define ST_LAUNCH(IPT)                                                                                                  \
-  hipLaunchKernelGGL((sample_token_kernel<IPT>), dim3(M), dim3(ST_THREADS), lds, STREAM(stream), logits, ldl, V_valid, \
-                     seen_off, seen_ids, penalty, temperature, top_p, u, vec, token, logp)
-  if (V_valid <= ST_THREADS * 8) ST_LAUNCH(8);
-  else if (V_valid <= ST_THREADS * 32) ST_LAUNCH(32);
-  else ST_LAUNCH(64);
+#define ST_LAUNCH(IPT)                                                                                                    \
+  launch<sample_token_kernel<IPT>>(lds, dim3(M), dim3(ST_THREADS), stream, logits, ldl, V_valid, seen_off, seen_ids, penalty, \
+                                   temperature, top_p, u, vec, token, logp)
+  if (V_valid <= ST_THREADS * 8) return ST_LAUNCH(8);
+  if (V_valid <= ST_THREADS * 32) return ST_LAUNCH(32);
+  return ST_LAUNCH(64);
 #undef ST_LAUNCH
-  RV_CHECK_LAUNCH();
-  return 0;
 }

@@ -1,9 +1,8 @@
 // HBM-bound kernels of the DPO step (norms, RoPE, SwiGLU, GELU, transposes, splice, optimizer).
 // All bf16 traffic is 16 bytes per lane (8 x bf16); accumulation in fp32.
 #include "common.hpp"
+#include "host.hpp"
 #include "rlaifv_hip.h"
-
-#include <stdlib.h>
 
 namespace {
 
@@ -1108,8 +1107,6 @@ inline int grid_for(long work, int block, int cap = 4096) {
 
 }  // namespace
 
-#define STREAM(s) ((hipStream_t)(s))
-
 // A gradient exchange seen from ONE GPU: `n_wg` persistent 256-thread workgroups (the footprint of n_wg RCCL channels -
 // one CU each, for as long as the bucket lasts) stream  dst[i] = a[i] + b[i]  (the receive-reduce-send of a ring step:
 // two 16-byte loads and one 16-byte store per 8 gradients).  bench.py launches it on a side stream at every
@@ -1146,16 +1143,63 @@ __global__ __launch_bounds__(256) void reduce_copy_persistent_kernel(const u32x4
   }
 }
 
+// ---- launch geometry and the launches that several entry points share ----
+// one workgroup per row, at most 8192 of them (the kernels stride over the rows)
+static dim3 row_grid(int rows) { return dim3(min(rows, 8192)); }
+
+// out[j] (+)= sum over the nb rows of partial[.][j], j < d; the rows are ldp floats apart
+static int launch_reduce_partials(const float* partial, int nb, int d, int ldp, void* out, int accumulate, void* stream) {
+  return launch<reduce_partials_kernel>(0, dim3((d + 31) / 32), dim3(256), stream, partial, nb, d, ldp, (bf16_t*)out, accumulate);
+}
+
+// Kernel(tensors..., work) over a flat range of `work` items, one per thread: the GELU pair (work = n / 8) and the casts
+template <auto Kernel, class... T>
+static int launch_flat(long work, int cap, void* stream, T... tensors) {
+  if (work == 0) return 0;
+  return launch<Kernel>(0, dim3(grid_for(work, 256, cap)), dim3(256), stream, tensors..., work);
+}
+
+// rv_rmsnorm_bwd (XT = bf16_t) and rv_rmsnorm_bwd_f32x (XT = float), after their own argument checks
+template <typename XT>
+static int rmsnorm_bwd(const void* dy, long lddy, const XT* x, long ldx, const int* row_idx, const void* w, const float* rstd,
+                       const void* dres, long lddres, void* dx, long lddx, float* dw_partial, void* dw, int dw_accumulate, int rows,
+                       int d, void* stream) {
+  if (rows == 0) return 0;
+  const int nb = rv_rmsnorm_bwd_nblocks(rows);
+  if (const int rc = launch<rmsnorm_bwd_kernel<XT>>(0, dim3(nb), dim3(256), stream, (const bf16_t*)dy, lddy, x, ldx, row_idx, (const bf16_t*)w,
+                                                    rstd, (const bf16_t*)dres, lddres, (bf16_t*)dx, lddx, dw_partial, rows, d))
+    return rc;
+  return launch_reduce_partials(dw_partial, nb, d, d, dw, dw_accumulate, stream);
+}
+
+// rv_layernorm_fwd (XT = bf16_t) and rv_layernorm_fwd_f32in (XT = float), after their own argument checks
+template <typename XT>
+static int layernorm_fwd(const XT* x, long ldx, const void* w, const void* b, void* y, long ldy, int rows, int d, float eps,
+                         void* stream) {
+  if (rows == 0) return 0;
+  return launch<layernorm_fwd_kernel<XT>>(0, row_grid(rows), dim3(256), stream, x, ldx, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, ldy,
+                                          rows, d, eps);
+}
+
+// f(std::integral_constant<int, IL>{}): the SwiGLU kernels take the layout (1 = interleaved gate / up columns) as a template argument
+template <class F>
+static int for_layout(int interleaved, F&& f) {
+  return interleaved ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
+}
+
+// the first pass of rv_grad_norm and rv_grad_sumsq: partial[1024] = per-workgroup sums of squares
+static int launch_sumsq(const void* g, long n, float* partial, void* stream) {
+  return launch<sumsq_kernel>(0, dim3(1024), dim3(256), stream, (const bf16_t*)g, n / 8, partial);
+}
+
 extern "C" {
 
 int rv_rmsnorm_fwd(const void* x, long ldx, const int* row_idx, const void* w, void* y, long ldy, float* rstd,
                    int rows, int d, float eps, void* stream) {
   RV_REQUIRE(d % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "rv_rmsnorm_fwd: d/ld must be multiples of 8");
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(rmsnorm_fwd_kernel<false>, dim3(min(rows, 8192)), dim3(256), 0, STREAM(stream), (const bf16_t*)x, ldx,
-                     row_idx, (const bf16_t*)w, (bf16_t*)y, ldy, rstd, rows, d, eps, (bf16_t*)nullptr, 0u, 1.f, 0u);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<rmsnorm_fwd_kernel<false>>(0, row_grid(rows), dim3(256), stream, (const bf16_t*)x, ldx, row_idx, (const bf16_t*)w,
+                                           (bf16_t*)y, ldy, rstd, rows, d, eps, (bf16_t*)nullptr, 0u, 1.f, 0u);
 }
 
 int rv_rmsnorm_fwd_dropout(const void* x, long ldx, const int* row_idx, const void* w, void* y, long ldy, float* rstd,
@@ -1164,10 +1208,8 @@ int rv_rmsnorm_fwd_dropout(const void* x, long ldx, const int* row_idx, const vo
   RV_REQUIRE(yd != nullptr && p >= 0.f && p < 1.f, "rv_rmsnorm_fwd_dropout: yd required, 0 <= p < 1");
   if (rows == 0) return 0;
   const DropParams dp = drop_params(p, seed);
-  hipLaunchKernelGGL(rmsnorm_fwd_kernel<true>, dim3(min(rows, 8192)), dim3(256), 0, STREAM(stream), (const bf16_t*)x, ldx,
-                     row_idx, (const bf16_t*)w, (bf16_t*)y, ldy, rstd, rows, d, eps, (bf16_t*)yd, dp.thresh16, dp.inv_keep, dp.key);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<rmsnorm_fwd_kernel<true>>(0, row_grid(rows), dim3(256), stream, (const bf16_t*)x, ldx, row_idx, (const bf16_t*)w,
+                                          (bf16_t*)y, ldy, rstd, rows, d, eps, (bf16_t*)yd, dp.thresh16, dp.inv_keep, dp.key);
 }
 
 // workgroups (= fp32 partial rows of dw): 1024 measured best at 27 k rows (512: 278 us, 1024: 239 us, 2048: 296 us, 4096: 377 us - the partial-sum pass grows)
@@ -1181,16 +1223,7 @@ int rv_rmsnorm_bwd(const void* dy, long lddy, const void* x, long ldx, const int
                    void* dw, int dw_accumulate, int rows, int d, void* stream) {
   RV_REQUIRE(d % 8 == 0 && d <= 2048 * RMS_MAX_ITERS, "rv_rmsnorm_bwd: d must be a multiple of 8 and <= 8192");
   RV_REQUIRE(lddy % 8 == 0 && ldx % 8 == 0 && lddx % 8 == 0 && lddres % 8 == 0, "rv_rmsnorm_bwd: ld alignment");
-  if (rows == 0) return 0;
-  const int nb = rv_rmsnorm_bwd_nblocks(rows);
-  hipLaunchKernelGGL(rmsnorm_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, STREAM(stream), (const bf16_t*)dy, lddy,
-                     (const bf16_t*)x, ldx, row_idx, (const bf16_t*)w, rstd, (const bf16_t*)dres, lddres,
-                     (bf16_t*)dx, lddx, dw_partial, rows, d);
-  RV_CHECK_LAUNCH();
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((d + 31) / 32), dim3(256), 0, STREAM(stream), dw_partial, nb, d, d,
-                     (bf16_t*)dw, dw_accumulate);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return rmsnorm_bwd(dy, lddy, (const bf16_t*)x, ldx, row_idx, w, rstd, dres, lddres, dx, lddx, dw_partial, dw, dw_accumulate, rows, d, stream);
 }
 
 int rv_rmsnorm_bwd_f32x(const void* dy, long lddy, const float* x, long ldx, const int* row_idx, const void* w,
@@ -1198,15 +1231,7 @@ int rv_rmsnorm_bwd_f32x(const void* dy, long lddy, const float* x, long ldx, con
                         void* dw, int dw_accumulate, int rows, int d, void* stream) {
   RV_REQUIRE(d % 8 == 0 && d <= 2048 * RMS_MAX_ITERS, "rv_rmsnorm_bwd_f32x: d must be a multiple of 8 and <= 8192");
   RV_REQUIRE(lddy % 8 == 0 && ldx % 4 == 0 && lddx % 8 == 0 && lddres % 8 == 0, "rv_rmsnorm_bwd_f32x: ld alignment");
-  if (rows == 0) return 0;
-  const int nb = rv_rmsnorm_bwd_nblocks(rows);
-  hipLaunchKernelGGL(rmsnorm_bwd_kernel<float>, dim3(nb), dim3(256), 0, STREAM(stream), (const bf16_t*)dy, lddy, x, ldx, row_idx,
-                     (const bf16_t*)w, rstd, (const bf16_t*)dres, lddres, (bf16_t*)dx, lddx, dw_partial, rows, d);
-  RV_CHECK_LAUNCH();
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((d + 31) / 32), dim3(256), 0, STREAM(stream), dw_partial, nb, d, d,
-                     (bf16_t*)dw, dw_accumulate);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return rmsnorm_bwd(dy, lddy, x, ldx, row_idx, w, rstd, dres, lddres, dx, lddx, dw_partial, dw, dw_accumulate, rows, d, stream);
 }
 
 int rv_rmsnorm_fwd_f32(const float* x, long ldx, const int* row_idx, const void* add, long ldadd, float* xout, long ldxout,
@@ -1216,41 +1241,27 @@ int rv_rmsnorm_fwd_f32(const float* x, long ldx, const int* row_idx, const void*
   RV_REQUIRE(y != nullptr || add != nullptr, "rv_rmsnorm_fwd_f32: nothing to write");
   if (rows == 0) return 0;
   if (add)
-    hipLaunchKernelGGL(rmsnorm_fwd_f32_kernel<true>, dim3(min(rows, 8192)), dim3(256), 0, STREAM(stream), x, ldx, row_idx,
-                       (const bf16_t*)add, ldadd, xout, ldxout, (const bf16_t*)w, (bf16_t*)y, ldy, rstd, rows, d, eps);
-  else
-    hipLaunchKernelGGL(rmsnorm_fwd_f32_kernel<false>, dim3(min(rows, 8192)), dim3(256), 0, STREAM(stream), x, ldx, row_idx,
-                       (const bf16_t*)nullptr, 0L, (float*)nullptr, 0L, (const bf16_t*)w, (bf16_t*)y, ldy, rstd, rows, d, eps);
-  RV_CHECK_LAUNCH();
-  return 0;
+    return launch<rmsnorm_fwd_f32_kernel<true>>(0, row_grid(rows), dim3(256), stream, x, ldx, row_idx, (const bf16_t*)add, ldadd, xout, ldxout,
+                                                (const bf16_t*)w, (bf16_t*)y, ldy, rstd, rows, d, eps);
+  return launch<rmsnorm_fwd_f32_kernel<false>>(0, row_grid(rows), dim3(256), stream, x, ldx, row_idx, (const bf16_t*)nullptr, 0L,
+                                               (float*)nullptr, 0L, (const bf16_t*)w, (bf16_t*)y, ldy, rstd, rows, d, eps);
 }
 
 int rv_add_f32_bf16(const float* x, const void* b, float* out, long n, void* stream) {
   RV_REQUIRE(n % 8 == 0, "rv_add_f32_bf16: n%8");
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(add_f32_bf16_kernel, dim3(grid_for(n / 8, 256, 8192)), dim3(256), 0, STREAM(stream), x, (const bf16_t*)b, out, n / 8);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch_flat<add_f32_bf16_kernel>(n / 8, 8192, stream, x, (const bf16_t*)b, out);
 }
 
 int rv_layernorm_fwd(const void* x, long ldx, const void* w, const void* b, void* y, long ldy, int rows, int d,
                      float eps, void* stream) {
   RV_REQUIRE(d % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "rv_layernorm_fwd: alignment");
-  if (rows == 0) return 0;
-  hipLaunchKernelGGL(layernorm_fwd_kernel<bf16_t>, dim3(min(rows, 8192)), dim3(256), 0, STREAM(stream), (const bf16_t*)x, ldx,
-                     (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, ldy, rows, d, eps);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return layernorm_fwd((const bf16_t*)x, ldx, w, b, y, ldy, rows, d, eps, stream);
 }
 
 int rv_layernorm_fwd_f32in(const float* x, long ldx, const void* w, const void* b, void* y, long ldy, int rows, int d,
                            float eps, void* stream) {
   RV_REQUIRE(d % 8 == 0 && ldx % 4 == 0 && ldy % 8 == 0, "rv_layernorm_fwd_f32in: alignment");
-  if (rows == 0) return 0;
-  hipLaunchKernelGGL(layernorm_fwd_kernel<float>, dim3(min(rows, 8192)), dim3(256), 0, STREAM(stream), x, ldx,
-                     (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, ldy, rows, d, eps);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return layernorm_fwd(x, ldx, w, b, y, ldy, rows, d, eps, stream);
 }
 
 int rv_layernorm_bwd(const void* dy, long lddy, const void* x, long ldx, int x_period, const void* w, void* dx, long lddx,
@@ -1259,37 +1270,26 @@ int rv_layernorm_bwd(const void* dy, long lddy, const void* x, long ldx, int x_p
   RV_REQUIRE(lddy % 8 == 0 && ldx % 8 == 0 && lddx % 8 == 0, "rv_layernorm_bwd: ld alignment");
   if (rows == 0) return 0;
   const int nb = rv_rmsnorm_bwd_nblocks(rows);
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(nb), dim3(256), 0, STREAM(stream), (const bf16_t*)dy, lddy, (const bf16_t*)x,
-                     ldx, x_period, (const bf16_t*)w, (bf16_t*)dx, lddx, partial, rows, d, eps);
-  RV_CHECK_LAUNCH();
+  if (const int rc = launch<layernorm_bwd_kernel>(0, dim3(nb), dim3(256), stream, (const bf16_t*)dy, lddy, (const bf16_t*)x, ldx, x_period,
+                                                  (const bf16_t*)w, (bf16_t*)dx, lddx, partial, rows, d, eps))
+    return rc;
   // partial = [nb][2d] (gain | bias halves): each half is reduced over its own d columns, rows 2d floats apart
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((d + 31) / 32), dim3(256), 0, STREAM(stream), partial, nb, d, 2 * d,
-                     (bf16_t*)dw, accumulate);
-  RV_CHECK_LAUNCH();
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((d + 31) / 32), dim3(256), 0, STREAM(stream), partial + d, nb, d, 2 * d,
-                     (bf16_t*)db, accumulate);
-  RV_CHECK_LAUNCH();
-  return 0;
+  if (const int rc = launch_reduce_partials(partial, nb, d, 2 * d, dw, accumulate, stream)) return rc;
+  return launch_reduce_partials(partial + d, nb, d, 2 * d, db, accumulate, stream);
 }
 
 int rv_add_rows(const void* x, long ldx, const void* p, long ldp, int period, void* y, long ldy, long rows, int d,
                 void* stream) {
   RV_REQUIRE(d % 8 == 0 && ldx % 8 == 0 && ldp % 8 == 0 && ldy % 8 == 0 && period > 0, "rv_add_rows: alignment / period");
   if (rows == 0) return 0;
-  const long total = rows * (d / 8);
-  hipLaunchKernelGGL(add_rows_kernel, dim3((unsigned)min((total + 255) / 256, (long)8192)), dim3(256), 0, STREAM(stream),
-                     (const bf16_t*)x, ldx, (const bf16_t*)p, ldp, period, (bf16_t*)y, ldy, rows, d);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<add_rows_kernel>(0, dim3(grid_for(rows * (d / 8), 256, 8192)), dim3(256), stream, (const bf16_t*)x, ldx, (const bf16_t*)p,
+                                 ldp, period, (bf16_t*)y, ldy, rows, d);
 }
 
 int rv_sum_rows_periodic(const void* x, long ldx, int period, int reps, void* y, long ldy, int d, void* stream) {
   RV_REQUIRE(d % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && period > 0 && reps > 0, "rv_sum_rows_periodic: alignment");
-  const long total = (long)period * (d / 8);
-  hipLaunchKernelGGL(sum_rows_periodic_kernel, dim3((unsigned)min((total + 255) / 256, (long)8192)), dim3(256), 0,
-                     STREAM(stream), (const bf16_t*)x, ldx, period, reps, (bf16_t*)y, ldy, d);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<sum_rows_periodic_kernel>(0, dim3(grid_for((long)period * (d / 8), 256, 8192)), dim3(256), stream, (const bf16_t*)x, ldx,
+                                          period, reps, (bf16_t*)y, ldy, d);
 }
 
 int rv_rope_inplace(void* x, long ld, const float* cos_tab, const float* sin_tab, const int* pos, long n_tok, int L,
@@ -1297,23 +1297,17 @@ int rv_rope_inplace(void* x, long ld, const float* cos_tab, const float* sin_tab
   RV_REQUIRE(hd % 16 == 0 && ld % 8 == 0, "rv_rope_inplace: hd%16, ld%8");
   const long total = n_tok * n_heads_total * (hd / 16);
   if (total == 0) return 0;
-  hipLaunchKernelGGL(rope_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, STREAM(stream), (bf16_t*)x, ld,
-                     cos_tab, sin_tab, pos, n_tok, L, n_heads_total, hd, backward ? -1.f : 1.f);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<rope_kernel>(0, dim3(grid_for(total, 256, 16384)), dim3(256), stream, (bf16_t*)x, ld, cos_tab, sin_tab, pos, n_tok, L,
+                             n_heads_total, hd, backward ? -1.f : 1.f);
 }
 
 int rv_swiglu_fwd(const void* gu, long ldgu, void* act, long lda, long rows, int f, int interleaved, void* stream) {
   RV_REQUIRE(f % 8 == 0 && ldgu % 8 == 0 && lda % 8 == 0, "rv_swiglu_fwd: alignment");
   if (rows == 0) return 0;
-  if (interleaved)
-    hipLaunchKernelGGL(swiglu_fwd_kernel<1>, dim3(grid_for(rows * (f / 8), 256, 16384)), dim3(256), 0, STREAM(stream),
-                       (const bf16_t*)gu, ldgu, (bf16_t*)act, lda, rows, f);
-  else
-    hipLaunchKernelGGL(swiglu_fwd_kernel<0>, dim3(grid_for(rows * (f / 8), 256, 16384)), dim3(256), 0, STREAM(stream),
-                       (const bf16_t*)gu, ldgu, (bf16_t*)act, lda, rows, f);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return for_layout(interleaved, [&](auto IL) {
+    return launch<swiglu_fwd_kernel<decltype(IL)::value>>(0, dim3(grid_for(rows * (f / 8), 256, 16384)), dim3(256), stream, (const bf16_t*)gu,
+                                                          ldgu, (bf16_t*)act, lda, rows, f, (bf16_t*)nullptr, 0u, 1.f, 0u);
+  });
 }
 
 int rv_swiglu_fwd_dropout(const void* gu, long ldgu, void* act, long lda, long rows, int f, void* actd, float p, int seed,
@@ -1322,41 +1316,27 @@ int rv_swiglu_fwd_dropout(const void* gu, long ldgu, void* act, long lda, long r
   RV_REQUIRE(actd != nullptr && p >= 0.f && p < 1.f, "rv_swiglu_fwd_dropout: actd required, 0 <= p < 1");
   if (rows == 0) return 0;
   const DropParams dp = drop_params(p, seed);
-  hipLaunchKernelGGL((swiglu_fwd_kernel<0, true>), dim3(grid_for(rows * (f / 8), 256, 16384)), dim3(256), 0, STREAM(stream),
-                     (const bf16_t*)gu, ldgu, (bf16_t*)act, lda, rows, f, (bf16_t*)actd, dp.thresh16, dp.inv_keep, dp.key);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<swiglu_fwd_kernel<0, true>>(0, dim3(grid_for(rows * (f / 8), 256, 16384)), dim3(256), stream, (const bf16_t*)gu, ldgu,
+                                            (bf16_t*)act, lda, rows, f, (bf16_t*)actd, dp.thresh16, dp.inv_keep, dp.key);
 }
 
 int rv_swiglu_bwd(const void* dact, long ldd, const void* gu, long ldgu, void* dgu, long lddgu, long rows, int f,
                   int interleaved, void* stream) {
   RV_REQUIRE(f % 8 == 0 && ldgu % 8 == 0 && ldd % 8 == 0 && lddgu % 8 == 0, "rv_swiglu_bwd: alignment");
   if (rows == 0) return 0;
-  if (interleaved)
-    hipLaunchKernelGGL(swiglu_bwd_kernel<1>, dim3(grid_for(rows * (f / 8), 256, 16384)), dim3(256), 0, STREAM(stream),
-                       (const bf16_t*)dact, ldd, (const bf16_t*)gu, ldgu, (bf16_t*)dgu, lddgu, rows, f);
-  else
-    hipLaunchKernelGGL(swiglu_bwd_kernel<0>, dim3(grid_for(rows * (f / 8), 256, 16384)), dim3(256), 0, STREAM(stream),
-                       (const bf16_t*)dact, ldd, (const bf16_t*)gu, ldgu, (bf16_t*)dgu, lddgu, rows, f);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return for_layout(interleaved, [&](auto IL) {
+    return launch<swiglu_bwd_kernel<decltype(IL)::value>>(0, dim3(grid_for(rows * (f / 8), 256, 16384)), dim3(256), stream,
+                                                          (const bf16_t*)dact, ldd, (const bf16_t*)gu, ldgu, (bf16_t*)dgu, lddgu, rows, f);
+  });
 }
 
 int rv_gelu_fwd(const void* x, void* y, long n, void* stream) {
   RV_REQUIRE(n % 8 == 0, "rv_gelu_fwd: n%8");
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(gelu_fwd_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0, STREAM(stream), (const bf16_t*)x,
-                     (bf16_t*)y, n / 8);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch_flat<gelu_fwd_kernel>(n / 8, 4096, stream, (const bf16_t*)x, (bf16_t*)y);
 }
 int rv_gelu_bwd(const void* dy, const void* x, void* dx, long n, void* stream) {
   RV_REQUIRE(n % 8 == 0, "rv_gelu_bwd: n%8");
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0, STREAM(stream), (const bf16_t*)dy,
-                     (const bf16_t*)x, (bf16_t*)dx, n / 8);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch_flat<gelu_bwd_kernel>(n / 8, 4096, stream, (const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx);
 }
 
 int rv_dropout(const void* x, void* y, void* acc, long n, float p, int seed, void* stream) {
@@ -1365,85 +1345,65 @@ int rv_dropout(const void* x, void* y, void* acc, long n, float p, int seed, voi
   RV_REQUIRE(y != nullptr || acc != nullptr, "rv_dropout: need an output (y) or an accumulator (acc)");
   if (n == 0) return 0;
   const DropParams dp = drop_params(p, seed);                           // 16 random bits per element
-  hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0, STREAM(stream), (const bf16_t*)x,
-                     (bf16_t*)y, (bf16_t*)acc, n / 8, dp.thresh16, dp.inv_keep, dp.key);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<dropout_kernel>(0, dim3(grid_for(n / 8, 256)), dim3(256), stream, (const bf16_t*)x, (bf16_t*)y, (bf16_t*)acc, n / 8,
+                                dp.thresh16, dp.inv_keep, dp.key);
 }
 
 int rv_resize_h_u8(const void* src, int H, int W, int y0, int rows, const int* bounds, const int* kk, int ksize, int out_w,
                    void* tmp, void* stream) {
   RV_REQUIRE(H > 0 && W > 0 && rows > 0 && y0 >= 0 && y0 + rows <= H && ksize > 0 && out_w > 0, "rv_resize_h_u8: bad sizes");
   const long n = (long)rows * out_w * 3;
-  hipLaunchKernelGGL(resize_h_u8_kernel, dim3(grid_for(n, 256)), dim3(256), 0, STREAM(stream), (const uint8_t*)src, W, y0,
-                     rows, bounds, kk, ksize, out_w, (uint8_t*)tmp);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<resize_h_u8_kernel>(0, dim3(grid_for(n, 256)), dim3(256), stream, (const uint8_t*)src, W, y0, rows, bounds, kk, ksize,
+                                    out_w, (uint8_t*)tmp);
 }
 int rv_resize_v_norm_u8(const void* tmp, int rows, int out_w, const int* bounds, const int* kk, int ksize, int out_h,
                         const float* table, float* out, void* stream) {
   RV_REQUIRE(rows > 0 && out_w > 0 && out_h > 0 && ksize > 0, "rv_resize_v_norm_u8: bad sizes");
   const long n = 3L * out_h * out_w;
-  hipLaunchKernelGGL(resize_v_norm_u8_kernel, dim3(grid_for(n, 256)), dim3(256), 0, STREAM(stream), (const uint8_t*)tmp,
-                     out_w, bounds, kk, ksize, out_h, table, out);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<resize_v_norm_u8_kernel>(0, dim3(grid_for(n, 256)), dim3(256), stream, (const uint8_t*)tmp, out_w, bounds, kk, ksize,
+                                         out_h, table, out);
 }
 
 int rv_transpose(const void* in, long ld_in, void* out, long ldo, int R, int C, void* stream) {
   RV_REQUIRE(C % 8 == 0 && ld_in % 8 == 0 && ldo % 8 == 0, "rv_transpose: C, ld_in, ldo must be multiples of 8");
   RV_REQUIRE(ldo >= ((R + 63) / 64) * 64, "rv_transpose: ldo must be >= roundup(R,64)");
   if (R == 0 || C == 0) return 0;
-  hipLaunchKernelGGL(transpose_kernel, dim3((C + 63) / 64, (R + 63) / 64), dim3(256), 0, STREAM(stream),
-                     (const bf16_t*)in, ld_in, (bf16_t*)out, ldo, R, C);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<transpose_kernel>(0, dim3((C + 63) / 64, (R + 63) / 64), dim3(256), stream, (const bf16_t*)in, ld_in, (bf16_t*)out, ldo,
+                                  R, C);
 }
 
 int rv_splice_fwd(const int* src, const void* embed, const void* feats, void* out, long n_rows, int d, void* stream) {
   RV_REQUIRE(d % 8 == 0, "rv_splice_fwd: d%8");
   if (n_rows == 0) return 0;
-  hipLaunchKernelGGL(splice_fwd_kernel, dim3(grid_for(n_rows * (d / 8), 256, 16384)), dim3(256), 0, STREAM(stream), src,
-                     (const bf16_t*)embed, (const bf16_t*)feats, (bf16_t*)out, n_rows, d);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<splice_fwd_kernel>(0, dim3(grid_for(n_rows * (d / 8), 256, 16384)), dim3(256), stream, src, (const bf16_t*)embed,
+                                   (const bf16_t*)feats, (bf16_t*)out, n_rows, d);
 }
 
 int rv_embed_bwd(const int* uniq_ids, const int* seg_off, const int* pos_sorted, int n_uniq, const void* dx, void* dW,
                  int d, void* stream) {
   RV_REQUIRE(d % 8 == 0, "rv_embed_bwd: d%8");
   if (n_uniq == 0) return 0;
-  hipLaunchKernelGGL(embed_bwd_kernel, dim3(n_uniq), dim3(256), 0, STREAM(stream), uniq_ids, seg_off, pos_sorted,
-                     (const bf16_t*)dx, (bf16_t*)dW, d);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<embed_bwd_kernel>(0, dim3(n_uniq), dim3(256), stream, uniq_ids, seg_off, pos_sorted, (const bf16_t*)dx, (bf16_t*)dW, d);
 }
 
 int rv_feat_grad(const int* src_a, const int* src_b, const void* dx, void* dfeat, long n_rows, int d, void* stream) {
   RV_REQUIRE(d % 8 == 0, "rv_feat_grad: d%8");
   if (n_rows == 0) return 0;
-  hipLaunchKernelGGL(feat_grad_kernel, dim3(grid_for(n_rows * (d / 8), 256, 16384)), dim3(256), 0, STREAM(stream), src_a,
-                     src_b, (const bf16_t*)dx, (bf16_t*)dfeat, n_rows, d);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<feat_grad_kernel>(0, dim3(grid_for(n_rows * (d / 8), 256, 16384)), dim3(256), stream, src_a, src_b, (const bf16_t*)dx,
+                                  (bf16_t*)dfeat, n_rows, d);
 }
 
 int rv_gather_rows(const void* in, long ld_in, const int* idx, void* out, long ld_out, long n_rows, int d, int scatter,
                    void* stream) {
   RV_REQUIRE(d % 8 == 0 && ld_in % 8 == 0 && ld_out % 8 == 0, "rv_gather_rows: alignment");
   if (n_rows == 0) return 0;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(n_rows * (d / 8), 256, 16384)), dim3(256), 0, STREAM(stream),
-                     (const bf16_t*)in, ld_in, idx, (bf16_t*)out, ld_out, n_rows, d, scatter);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<gather_rows_kernel>(0, dim3(grid_for(n_rows * (d / 8), 256, 16384)), dim3(256), stream, (const bf16_t*)in, ld_in, idx,
+                                    (bf16_t*)out, ld_out, n_rows, d, scatter);
 }
 
 int rv_colsum(const void* dy, long ld, void* db, int M, int N, void* stream) {
   if (N == 0) return 0;
-  hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64), dim3(1024), 0, STREAM(stream), (const bf16_t*)dy, ld,
-                     (bf16_t*)db, M, N);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<colsum_kernel>(0, dim3((N + 63) / 64), dim3(1024), stream, (const bf16_t*)dy, ld, (bf16_t*)db, M, N);
 }
 
 int rv_im2col_patches(const float* pixels, void* out, int B, int image_size, int patch, int Kp, void* stream) {
@@ -1451,55 +1411,38 @@ int rv_im2col_patches(const float* pixels, void* out, int B, int image_size, int
   const int g = image_size / patch;
   const long total = (long)B * g * g * Kp;
   if (total == 0) return 0;
-  hipLaunchKernelGGL(im2col_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, STREAM(stream), pixels,
-                     (bf16_t*)out, B, image_size, patch, Kp);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<im2col_kernel>(0, dim3(grid_for(total, 256, 16384)), dim3(256), stream, pixels, (bf16_t*)out, B, image_size, patch, Kp);
 }
 
 int rv_clip_assemble(const void* patch, const void* cls, const void* pos, void* x, int B, int P, int d, void* stream) {
   RV_REQUIRE(d % 8 == 0, "rv_clip_assemble: d%8");
   if (B == 0) return 0;
-  hipLaunchKernelGGL(clip_assemble_kernel, dim3(grid_for((long)B * (P + 1) * (d / 8), 256)), dim3(256), 0,
-                     STREAM(stream), (const bf16_t*)patch, (const bf16_t*)cls, (const bf16_t*)pos, (bf16_t*)x, B, P, d);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<clip_assemble_kernel>(0, dim3(grid_for((long)B * (P + 1) * (d / 8), 256)), dim3(256), stream, (const bf16_t*)patch,
+                                      (const bf16_t*)cls, (const bf16_t*)pos, (bf16_t*)x, B, P, d);
 }
 
 int rv_sumsq_nblocks(void) { return 1024; }
 
 int rv_grad_norm(const void* g, long n, float* partial, float max_norm, float pre_scale, float* out2, void* stream) {
   RV_REQUIRE(n % 8 == 0, "rv_grad_norm: n%8");
-  hipLaunchKernelGGL(sumsq_kernel, dim3(1024), dim3(256), 0, STREAM(stream), (const bf16_t*)g, n / 8, partial);
-  RV_CHECK_LAUNCH();
-  hipLaunchKernelGGL(gradnorm_finish_kernel, dim3(1), dim3(256), 0, STREAM(stream), partial, 1024, max_norm, pre_scale,
-                     out2);
-  RV_CHECK_LAUNCH();
-  return 0;
+  if (const int rc = launch_sumsq(g, n, partial, stream)) return rc;
+  return launch<gradnorm_finish_kernel>(0, dim3(1), dim3(256), stream, partial, 1024, max_norm, pre_scale, out2);
 }
 
 int rv_grad_sumsq(const void* g, long n, float* partial, float* out1, int accumulate, void* stream) {
   RV_REQUIRE(n % 8 == 0, "rv_grad_sumsq: n%8");
-  hipLaunchKernelGGL(sumsq_kernel, dim3(1024), dim3(256), 0, STREAM(stream), (const bf16_t*)g, n / 8, partial);
-  RV_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sumsq_finish_kernel, dim3(1), dim3(256), 0, STREAM(stream), partial, 1024, out1, accumulate);
-  RV_CHECK_LAUNCH();
-  return 0;
+  if (const int rc = launch_sumsq(g, n, partial, stream)) return rc;
+  return launch<sumsq_finish_kernel>(0, dim3(1), dim3(256), stream, partial, 1024, out1, accumulate);
 }
 
 int rv_clip_from_sumsq(const float* sumsq, float max_norm, float pre_scale, float* out2, void* stream) {
-  hipLaunchKernelGGL(clip_from_sumsq_kernel, dim3(1), dim3(1), 0, STREAM(stream), sumsq, max_norm, pre_scale, out2);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<clip_from_sumsq_kernel>(0, dim3(1), dim3(1), stream, sumsq, max_norm, pre_scale, out2);
 }
 
 int rv_grad_accum(float* acc, void* g, long n, int mode, float scale, void* stream) {
   RV_REQUIRE(n % 8 == 0 && mode >= 0 && mode <= 2, "rv_grad_accum: n % 8 == 0, mode in 0..2");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(grad_accum_kernel, dim3(grid_for(n / 8, 256, 8192)), dim3(256), 0, STREAM(stream), acc, (bf16_t*)g,
-                     n / 8, mode, scale);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<grad_accum_kernel>(0, dim3(grid_for(n / 8, 256, 8192)), dim3(256), stream, acc, (bf16_t*)g, n / 8, mode, scale);
 }
 
 int rv_adamw_step(void* p, float* master, float* m, float* v, const void* g, long n, float lr, float beta1, float beta2,
@@ -1508,19 +1451,14 @@ int rv_adamw_step(void* p, float* master, float* m, float* v, const void* g, lon
   if (n == 0) return 0;
   const float bc1 = 1.f - powf(beta1, (float)step);
   const float bc2 = 1.f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 8, 256, 8192)), dim3(256), 0, STREAM(stream), (bf16_t*)p, master, m,
-                     v, (const bf16_t*)g, n / 8, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), clip);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<adamw_kernel>(0, dim3(grid_for(n / 8, 256, 8192)), dim3(256), stream, (bf16_t*)p, master, m, v, (const bf16_t*)g, n / 8, lr,
+                              beta1, beta2, eps, wd, bc1, sqrtf(bc2), clip);
 }
 
 int rv_logp_finish(const float* pmax, const float* psum, const float* tgt_logit, int nblk, int M, float* lse,
                    float* logp, void* stream) {
   if (M == 0) return 0;
-  hipLaunchKernelGGL(logp_finish_kernel, dim3((M + 3) / 4), dim3(256), 0, STREAM(stream), pmax, psum, tgt_logit, nblk,
-                     M, lse, logp);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<logp_finish_kernel>(0, dim3((M + 3) / 4), dim3(256), stream, pmax, psum, tgt_logit, nblk, M, lse, logp);
 }
 
 int rv_logp_finish_unpack(const float* pmax, const float* psum, const float* tgt_logit, int nblk, int M, const int* dst_a,
@@ -1530,10 +1468,8 @@ int rv_logp_finish_unpack(const float* pmax, const float* psum, const float* tgt
   RV_REQUIRE(nblk > 0 && M > 0 && n_per_token >= 0 && n_compact >= 0, "rv_logp_finish_unpack: nblk, M > 0; sizes >= 0");
   RV_REQUIRE(dst_a && dst_b && dst_c, "rv_logp_finish_unpack: the three destination tables are required (-1 = no slot)");
   RV_REQUIRE((per_token || n_per_token == 0) && (compact || n_compact == 0), "rv_logp_finish_unpack: NULL output with a non-zero size");
-  hipLaunchKernelGGL(logp_finish_unpack_kernel, dim3((M + 3) / 4), dim3(256), 0, STREAM(stream), pmax, psum, tgt_logit, nblk,
-                     M, dst_a, dst_b, dst_c, per_token, n_per_token, compact, n_compact);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<logp_finish_unpack_kernel>(0, dim3((M + 3) / 4), dim3(256), stream, pmax, psum, tgt_logit, nblk, M, dst_a, dst_b, dst_c,
+                                           per_token, n_per_token, compact, n_compact);
 }
 
 int rv_next_token_scores(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids,
@@ -1547,37 +1483,27 @@ int rv_next_token_scores(const float* logits, long ldl, int M, int V_valid, cons
   const bool pen = seen_off != nullptr && penalty != 1.0f;
   const size_t lds = pen ? (size_t)((V_valid + 31) / 32) * 4 : 0;
   RV_REQUIRE(lds <= 60000, "rv_next_token_scores: the seen-id bitmap (V_valid / 8 bytes) must fit in LDS");
-  hipLaunchKernelGGL(next_token_scores_kernel, dim3(M), dim3(256), lds, STREAM(stream), logits, ldl, V_valid, seen_off,
-                     seen_ids, penalty, want_ids, K, probs, logp, argmax, lse);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<next_token_scores_kernel>((int)lds, dim3(M), dim3(256), stream, logits, ldl, V_valid, seen_off, seen_ids, penalty, want_ids,
+                                          K, probs, logp, argmax, lse);
 }
 
 int rv_seq_sum(const float* logp, const float* weight, const int* seq_off, int n_seq, float* out_sum, float* out_cnt,
                void* stream) {
   if (n_seq == 0) return 0;
-  hipLaunchKernelGGL(seq_sum_kernel, dim3(n_seq), dim3(256), 0, STREAM(stream), logp, weight, seq_off, out_sum,
-                     out_cnt);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<seq_sum_kernel>(0, dim3(n_seq), dim3(256), stream, logp, weight, seq_off, out_sum, out_cnt);
 }
 
 int rv_dpo_loss(const float* seq_sum, const float* seq_cnt, const float* ref_win, const float* ref_rej, int B,
                 float beta, int use_average, float sft_weight, float dpo_weight, float* per_pair, float* scalars,
                 float* coef, void* stream) {
   RV_REQUIRE(B > 0, "rv_dpo_loss: B must be > 0");
-  hipLaunchKernelGGL(dpo_loss_kernel, dim3(1), dim3(256), 0, STREAM(stream), seq_sum, seq_cnt, ref_win, ref_rej, B,
-                     beta, use_average, sft_weight, dpo_weight, per_pair, scalars, coef);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<dpo_loss_kernel>(0, dim3(1), dim3(256), stream, seq_sum, seq_cnt, ref_win, ref_rej, B, beta, use_average, sft_weight,
+                                 dpo_weight, per_pair, scalars, coef);
 }
 
 int rv_row_coef(const float* coef, const int* seq_of_row, const float* weight, float* out, int n, void* stream) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(row_coef_kernel, dim3((n + 255) / 256), dim3(256), 0, STREAM(stream), coef, seq_of_row, weight,
-                     out, n);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<row_coef_kernel>(0, dim3((n + 255) / 256), dim3(256), stream, coef, seq_of_row, weight, out, n);
 }
 
 int rv_attn_delta(const void* dO, long lddo, const void* O, long ldo, float* delta, int S, int L, int H, int hd,
@@ -1585,35 +1511,22 @@ int rv_attn_delta(const void* dO, long lddo, const void* O, long ldo, float* del
   RV_REQUIRE(hd % 2 == 0, "rv_attn_delta: hd even");
   const long total = (long)S * L * H;
   if (total == 0) return 0;
-  hipLaunchKernelGGL(attn_delta_kernel, dim3(grid_for(total, 4, 16384)), dim3(256), 0, STREAM(stream),
-                     (const bf16_t*)dO, lddo, (const bf16_t*)O, ldo, delta, S, L, H, hd);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<attn_delta_kernel>(0, dim3(grid_for(total, 4, 16384)), dim3(256), stream, (const bf16_t*)dO, lddo, (const bf16_t*)O, ldo,
+                                   delta, S, L, H, hd);
 }
 
 int rv_cast_f32_to_bf16(const float* in, void* out, long n, void* stream) {
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, STREAM(stream), in,
-                     (bf16_t*)out, n);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch_flat<cast_f32_bf16_kernel>(n, 8192, stream, in, (bf16_t*)out);
 }
 int rv_cast_bf16_to_f32(const void* in, float* out, long n, void* stream) {
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, STREAM(stream),
-                     (const bf16_t*)in, out, n);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch_flat<cast_bf16_f32_kernel>(n, 8192, stream, (const bf16_t*)in, out);
 }
 
 int rv_reduce_copy_persistent(const void* a, const void* b, void* dst, long n, int n_wg, void* stream) {
   RV_REQUIRE(n % 8 == 0, "rv_reduce_copy_persistent: n must be a multiple of 8 bf16 elements");
   RV_REQUIRE(n_wg >= 1 && n_wg <= 256, "rv_reduce_copy_persistent: 1 <= n_wg <= 256");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(reduce_copy_persistent_kernel, dim3(n_wg), dim3(256), 0, STREAM(stream), (const u32x4_t*)a,
-                     (const u32x4_t*)b, (u32x4_t*)dst, n / 8);
-  RV_CHECK_LAUNCH();
-  return 0;
+  return launch<reduce_copy_persistent_kernel>(0, dim3(n_wg), dim3(256), stream, (const u32x4_t*)a, (const u32x4_t*)b, (u32x4_t*)dst, n / 8);
 }
 
 }  // extern "C"

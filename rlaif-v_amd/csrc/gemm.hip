@@ -1,9 +1,10 @@
 // C-ABI launchers for the bf16 NT GEMM and the fused LM-head log-prob kernels (gemm.hpp).
 #include "gemm.hpp"
+#include "host.hpp"
 #include "rlaifv_hip.h"
 
+#include <stdarg.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <initializer_list>
@@ -13,12 +14,14 @@ void rv_set_error(const char* msg) {
   strncpy(g_err, msg ? msg : "", sizeof(g_err) - 1);
   g_err[sizeof(g_err) - 1] = 0;
 }
+void rv_set_errorf(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+}
 
 // ---- A/B knobs: each is read through one accessor, from the first call of any entry point on ----
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
 // variants: 0 = 128x128x64 register staging, 1 = 128x128x64 global_load_lds, 2 = 256x256x32 ping-pong,
 // -1 (default) = pick 2 when the problem fills the chip with 256x256 tiles, else 1.
 static int g_default_variant = -1;
@@ -39,38 +42,12 @@ static int nn_mi16() {
   return g_mi16;
 }
 
-// ---- the one launch helper: raises the kernel's dynamic-LDS limit the first time THIS instantiation is launched (once per
-// process, as before), launches, and reports a failure of either step as rc 2 ----
-template <auto Kernel, class... Args>
-static int launch(int lds, dim3 grid, dim3 block, hipStream_t st, const Args&... args) {
-  static bool limit_raised = false;
-  if (lds > 0 && !limit_raised) {
-    const hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();                  // or the next launch's RV_CHECK_LAUNCH would report this one
-      snprintf(g_err, sizeof(g_err), "raising a kernel's dynamic-LDS limit to %d bytes: %s", lds, hipGetErrorString(e));
-      return 2;
-    }
-    limit_raised = true;
-  }
-  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
-  RV_CHECK_LAUNCH();
-  return 0;
-}
-
 static int tiles(int n, int tile) { return (n + tile - 1) / tile; }
 // the chip-fill rule of the 256x256 kernels (ops.py _fills_chip mirrors it)
 static bool fills_chip(const GemmShape& g) { return (long)tiles(g.M, G2_BM) * tiles(g.N, G2_BN) >= 192; }
 
 // ---- argument checks.  Every message names the entry point that was called. ----
-static int reject(const char* who, const char* what) {
-  snprintf(g_err, sizeof(g_err), "%s: %s", who, what);
-  return 1;
-}
-#define REQ(cond, what)                         \
-  do {                                          \
-    if (!(cond)) return reject(who, what);      \
-  } while (0)
+#define REQ(cond, what) RV_REQUIRE_AS(who, cond, what)
 #define CHECK(call)                             \
   do {                                          \
     if (call) return 1;                         \
@@ -87,7 +64,7 @@ static int check_align(const char* who, std::initializer_list<const void*> ptrs,
   uintptr_t bits = 0;
   for (const void* p : ptrs) bits |= (uintptr_t)p;
   if (bits & (uintptr_t)(bytes - 1)) {
-    snprintf(g_err, sizeof(g_err), "%s: %s must be %d-byte aligned", who, names, bytes);
+    rv_set_errorf("%s: %s must be %d-byte aligned", who, names, bytes);
     return 1;
   }
   return 0;
@@ -97,7 +74,7 @@ static int check_groups(const char* who, int group_cols, int group0, int N, int 
   if (group_cols == 0 || (group_cols % tile == 0 && group0 % tile == 0 && group0 >= 0 && group0 <= N &&
                           (N - (group0 ? group0 : group_cols)) % group_cols == 0))
     return 0;
-  snprintf(g_err, sizeof(g_err), "%s: group_cols / group0 must be multiples of %d that tile N (group0 + k * group_cols = N)", who, tile);
+  rv_set_errorf("%s: group_cols / group0 must be multiples of %d that tile N (group0 + k * group_cols = N)", who, tile);
   return 1;
 }
 static int check_p(const char* who, float p) {
@@ -128,26 +105,25 @@ static EpiStore epi_store(void* C, long ldc, const void* bias, const void* resid
 
 // ---- NT launchers: 128x128 tiles (STAGE 0 = register staging, 1 = LDS-DMA) and 256x256 ping-pong; EXT = second K segment ----
 template <int STAGE, class Epi, bool EXT = false>
-static int launch_gemm(const GemmShape& g, const Epi& epi, hipStream_t st) {
+static int launch_gemm(const GemmShape& g, const Epi& epi, void* st) {
   return launch<gemm_nt_kernel<STAGE, Epi, EXT>>(GEMM_LDS_BYTES, dim3(tiles(g.M, GEMM_BM) * tiles(g.N, GEMM_BN)), dim3(GEMM_THREADS),
                                                  st, g, epi);
 }
 template <class Epi, bool DMA_IN_MSEG, bool EXT = false>
-static int launch_gemm256(const GemmShape& g, const Epi& epi, hipStream_t st) {
+static int launch_gemm256(const GemmShape& g, const Epi& epi, void* st) {
   return launch<gemm_nt_256_kernel<Epi, DMA_IN_MSEG, EXT>>(4 * G2_STAGE_BYTES, dim3(tiles(g.M, G2_BM) * tiles(g.N, G2_BN)),
                                                            dim3(G2_THREADS), st, g, epi);
 }
 
 template <class Epi>
 static int dispatch(const char* who, const GemmShape& g, const Epi& epi, int variant, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   if (variant < 0) variant = g_default_variant;
   if (variant < 0) variant = fills_chip(g) ? 3 : 1;
   REQ(variant <= 3, "GEMM variant: 0..3");
-  if (variant == 3) return launch_gemm256<Epi, true>(g, epi, st);
-  if (variant == 2) return launch_gemm256<Epi, false>(g, epi, st);
-  if (variant == 1) return launch_gemm<1, Epi>(g, epi, st);
-  return launch_gemm<0, Epi>(g, epi, st);
+  if (variant == 3) return launch_gemm256<Epi, true>(g, epi, stream);
+  if (variant == 2) return launch_gemm256<Epi, false>(g, epi, stream);
+  if (variant == 1) return launch_gemm<1, Epi>(g, epi, stream);
+  return launch_gemm<0, Epi>(g, epi, stream);
 }
 
 // GEMMs with a second contraction segment (GemmShape::A2/B2/K2): the 256x256 ping-pong kernel when the problem
@@ -155,8 +131,8 @@ static int dispatch(const char* who, const GemmShape& g, const Epi& epi, int var
 template <class Epi>
 static int dispatch_ext(const GemmShape& g, const Epi& epi, void* stream) {
   if (fills_chip(g) && g.group_cols % G2_BN == 0 && g.group0 % G2_BN == 0)
-    return launch_gemm256<Epi, true, true>(g, epi, (hipStream_t)stream);
-  return launch_gemm<1, Epi, true>(g, epi, (hipStream_t)stream);
+    return launch_gemm256<Epi, true, true>(g, epi, stream);
+  return launch_gemm<1, Epi, true>(g, epi, stream);
 }
 
 // ---- the NN launcher: the 64-deep-A kernel when K allows (K % 64 == 0, K >= 512; with EXT also K2 % 64 == 0), with the
@@ -166,7 +142,7 @@ static int dispatch_ext(const GemmShape& g, const Epi& epi, void* stream) {
 // in .text, and the bytes of the TN kernels depend on where they lie: reordering shows up as four changed digests in
 // kernel_resources.py --digest, see that tool's docstring.) ----
 template <class Epi, bool EXT = false, bool PRE = false, bool A64_ONLY = PRE>
-static int launch_nn(const GemmShape& g, const Epi& epi, hipStream_t st) {
+static int launch_nn(const GemmShape& g, const Epi& epi, void* st) {
   static_assert(A64_ONLY || !PRE, "the adapter-first form has no 32-deep kernel");
   const dim3 grid(tiles(g.M, G2_BM) * tiles(g.N, G2_BN)), block(G2_THREADS);
   [[maybe_unused]] const bool a64 = A64_ONLY || (g.K % 64 == 0 && g.K >= 512 && (!EXT || g.K2 % 64 == 0));
@@ -180,7 +156,7 @@ static int launch_nn(const GemmShape& g, const Epi& epi, hipStream_t st) {
 // TN kernel: prefetch distance 3 (128 KiB LDS ring; distance 4 measured equal)
 template <class Epi>
 static int launch_gemm_tn(const bf16_t* P, long ldp, const bf16_t* Q, long ldq, int R, int I, int J, const Epi& epi,
-                          hipStream_t st, int splits = 1, int r_chunk = 0, long split_stride = 0, int bid0 = 0,
+                          void* st, int splits = 1, int r_chunk = 0, long split_stride = 0, int bid0 = 0,
                           int nblocks = 0) {
   constexpr int DIST = 3, LDS = (DIST + 1) * G2_STAGE_BYTES;
   const int gx = nblocks > 0 ? nblocks : tiles(I, 256) * tiles(J, 256);          // launch-order positions bid0 .. bid0 + gx - 1
@@ -271,7 +247,7 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int splits, i
     *(uint2*)(out + i * ldc + j) = o;
   }
 }
-static int launch_splitk_reduce(const float* ws, int splits, int I, int J, float alpha, void* out, long ldc, hipStream_t st) {
+static int launch_splitk_reduce(const float* ws, int splits, int I, int J, float alpha, void* out, long ldc, void* st) {
   const long blocks = ((long)I * J / 4 + 255) / 256;
   return launch<splitk_reduce_kernel>(0, dim3((int)(blocks < 2048 ? blocks : 2048)), dim3(256), st, ws, splits, I, J, alpha, (bf16_t*)out,
                                       ldc);
@@ -327,7 +303,7 @@ int rv_gemm_nt_bf16(const void* A, long lda, const void* B, long ldb, void* C, l
   // many rows, at most 256 columns, plain store: the streaming kernel (the rank-r side of LoRA)
   if (variant < 0 && g_default_variant < 0 && N % GSK_BN == 0 && N <= 256 && M >= 4096 && bias == nullptr &&
       residual == nullptr && act == RV_ACT_NONE && ((uintptr_t)C & 7) == 0)
-    return launch<gemm_nt_skinny_kernel>(GSK_LDS_BYTES, dim3(tiles(M, GSK_BM) * (N / GSK_BN)), dim3(256), (hipStream_t)stream, g,
+    return launch<gemm_nt_skinny_kernel>(GSK_LDS_BYTES, dim3(tiles(M, GSK_BM) * (N / GSK_BN)), dim3(256), stream, g,
                                          (bf16_t*)C, ldc, alpha);
   return dispatch(who, g, epi_store(C, ldc, bias, residual, ldr, act, alpha), variant, stream);
 }
@@ -347,7 +323,7 @@ int rv_gemm_tn_bf16(const void* P, long ldp, const void* Q, long ldq, void* C, l
   CHECK(check_ld(who, {ldp, ldq}, {ldc, residual ? ldr : 0}));
   CHECK(check_align(who, {P, Q}, 16, "P/Q"));
   return launch_gemm_tn((const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, R, I, J, epi_store(C, ldc, nullptr, residual, ldr, RV_ACT_NONE, alpha),
-                        (hipStream_t)stream);
+                        stream);
 }
 
 int rv_gemm_tn_workspace_floats(int R, int I, int J) {
@@ -365,14 +341,13 @@ int rv_gemm_tn_bf16_ws(const void* P, long ldp, const void* Q, long ldq, void* C
   CHECK(check_align(who, {P, Q, workspace}, 16, "P/Q/workspace"));
   CHECK(check_align(who, {C}, 8, "C (the tail reduce stores 4 bf16 at a time)"));
   const bf16_t *p_ = (const bf16_t*)P, *q_ = (const bf16_t*)Q;
-  hipStream_t st = (hipStream_t)stream;
   const TnTailPlan p = tn_tail_plan(R, I, J);
   const EpiStore epi = epi_store(C, ldc, nullptr, nullptr, 0, RV_ACT_NONE, 1.0f);
   if (p.splits <= 1 || workspace == nullptr || workspace_floats < (long)p.splits * p.tail * 65536)
-    return launch_gemm_tn(p_, ldp, q_, ldq, R, I, J, epi, st);
-  if (launch_gemm_tn(p_, ldp, q_, ldq, R, I, J, epi, st, 1, 0, 0, 0, p.full_blocks)) return 1;
-  if (launch_gemm_tn(p_, ldp, q_, ldq, R, I, J, EpiStoreF32{workspace, 256}, st, p.splits, p.r_chunk, -1, p.full_blocks, p.tail)) return 1;
-  return launch<tn_tail_reduce_kernel>(0, dim3(p.tail), dim3(256), st, (const float*)workspace, p.splits, p.tail, p.full_blocks, I, J,
+    return launch_gemm_tn(p_, ldp, q_, ldq, R, I, J, epi, stream);
+  if (launch_gemm_tn(p_, ldp, q_, ldq, R, I, J, epi, stream, 1, 0, 0, 0, p.full_blocks)) return 1;
+  if (launch_gemm_tn(p_, ldp, q_, ldq, R, I, J, EpiStoreF32{workspace, 256}, stream, p.splits, p.r_chunk, -1, p.full_blocks, p.tail)) return 1;
+  return launch<tn_tail_reduce_kernel>(0, dim3(p.tail), dim3(256), stream, (const float*)workspace, p.splits, p.tail, p.full_blocks, I, J,
                                        gemm_group(), (bf16_t*)C, ldc);
 }
 
@@ -398,7 +373,7 @@ static int nn_bias_act(const char* who, const void* A, long lda, const void* B, 
   REQ(N % 8 == 0 && N >= 8, "N must be a multiple of 8");
   CHECK(check_ld(who, {lda, ldb}, {ldc, residual ? ldr : 0}));
   CHECK(check_align(who, {A, B}, 16, "A/B"));
-  return launch_nn(shape(A, lda, B, ldb, M, N, K), epi_store(C, ldc, bias, residual, ldr, act, alpha), (hipStream_t)stream);
+  return launch_nn(shape(A, lda, B, ldb, M, N, K), epi_store(C, ldc, bias, residual, ldr, act, alpha), stream);
 }
 
 int rv_gemm_nn_bf16(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
@@ -426,7 +401,7 @@ int rv_gemm_nn_rope_bf16(const void* A, long lda, const void* B, long ldb, void*
   CHECK(check_align(who, {A, B, C, cos_tab, sin_tab}, 16, "operands and tables"));
   REQ(cos_tab && sin_tab && L > 0, "cos_tab, sin_tab and L > 0 required");
   const EpiStoreRope epi{(bf16_t*)C, ldc, cos_tab, sin_tab, pos, L, rope_cols};
-  return launch_nn<EpiStoreRope, false, false, true>(shape(A, lda, B, ldb, M, N, K), epi, (hipStream_t)stream);
+  return launch_nn<EpiStoreRope, false, false, true>(shape(A, lda, B, ldb, M, N, K), epi, stream);
 }
 
 int rv_gemm_nn_swiglu_bf16(const void* A, long lda, const void* B, long ldb, void* GU, long ldgu, void* ACT, long ldact,
@@ -438,7 +413,7 @@ int rv_gemm_nn_swiglu_bf16(const void* A, long lda, const void* B, long ldb, voi
   CHECK(check_ld(who, {lda, ldb, ldgu}, {ldact}));
   CHECK(check_align(who, {A, B, GU}, 16, "A/B/GU"));
   CHECK(check_align(who, {ACT}, 8, "ACT"));
-  return launch_nn(shape(A, lda, B, ldb, M, N, K), EpiSwiGLU{(bf16_t*)GU, ldgu, (bf16_t*)ACT, ldact}, (hipStream_t)stream);
+  return launch_nn(shape(A, lda, B, ldb, M, N, K), EpiSwiGLU{(bf16_t*)GU, ldgu, (bf16_t*)ACT, ldact}, stream);
 }
 
 int rv_gemm_nn_swiglu_bwd_bf16(const void* A, long lda, const void* B, long ldb, const void* GU, long ldgu, void* DGU,
@@ -449,7 +424,7 @@ int rv_gemm_nn_swiglu_bwd_bf16(const void* A, long lda, const void* B, long ldb,
   REQ(N % 8 == 0, "N (= ffn) must be a multiple of 8");
   CHECK(check_ld(who, {lda, ldb, ldgu, lddgu}, {}));
   CHECK(check_align(who, {A, B, GU, DGU}, 16, "A/B/GU/DGU"));
-  return launch_nn(shape(A, lda, B, ldb, M, N, K), EpiSwiGLUBwd{(const bf16_t*)GU, ldgu, (bf16_t*)DGU, lddgu}, (hipStream_t)stream);
+  return launch_nn(shape(A, lda, B, ldb, M, N, K), EpiSwiGLUBwd{(const bf16_t*)GU, ldgu, (bf16_t*)DGU, lddgu}, stream);
 }
 
 int rv_gemm_nn_lora_bf16(const void* A, long lda, const void* B, long ldb, const void* A2, long lda2, const void* B2,
@@ -463,7 +438,7 @@ int rv_gemm_nn_lora_bf16(const void* A, long lda, const void* B, long ldb, const
   CHECK(check_align(who, {A, B, A2, B2}, 16, "A/B/A2/B2"));
   CHECK(check_groups(who, group_cols, group0, N, G2_BN));
   const GemmShape g = shape_ext(A, lda, B, ldb, M, N, K, A2, lda2, B2, ldb2, K2, group_cols, group0);
-  return launch_nn<EpiStore, true>(g, epi_store(C, ldc, nullptr, residual, ldr, RV_ACT_NONE, 1.0f), (hipStream_t)stream);
+  return launch_nn<EpiStore, true>(g, epi_store(C, ldc, nullptr, residual, ldr, RV_ACT_NONE, 1.0f), stream);
 }
 
 // what the fused-adapter entries of the 64-deep-A kernel ask of K and K2
@@ -497,7 +472,7 @@ int rv_gemm_nn_lora_swiglu_bf16(const void* A, long lda, const void* B, long ldb
     epi.drop_inv_keep = d.inv_keep;
   }
   const GemmShape g = shape_ext(A, lda, B, ldb, M, N, K, A2, lda2, B2, ldb2, K2, 0, 0);
-  return launch_nn<EpiSwiGLU, true, false, true>(g, epi, (hipStream_t)stream);
+  return launch_nn<EpiSwiGLU, true, false, true>(g, epi, stream);
 }
 
 // Input gradient of an ADAPTER model's down projection with the SwiGLU backward in the epilogue: acc = d act = dy W + [mask](dt A) / (1 - p)
@@ -515,12 +490,12 @@ int rv_gemm_nn_lora_swiglu_bwd_bf16(const void* A, long lda, const void* B, long
   CHECK(check_align(who, {A, B, A2, B2, GU, DGU}, 16, "A/B/A2/B2/GU/DGU"));
   GemmShape g = shape_ext(A, lda, B, ldb, M, N, K, A2, lda2, B2, ldb2, K2, 0, 0);
   const EpiSwiGLUBwd epi{(const bf16_t*)GU, ldgu, (bf16_t*)DGU, lddgu};
-  if (p == 0.f) return launch_nn<EpiSwiGLUBwd, true, false, true>(g, epi, (hipStream_t)stream);
+  if (p == 0.f) return launch_nn<EpiSwiGLUBwd, true, false, true>(g, epi, stream);
   const DropParams d = drop_params(p, seed);
   g.pre_thresh16 = d.thresh16;
   g.pre_key = d.key;
   g.pre_inv_keep = d.inv_keep;
-  return launch_nn<EpiSwiGLUBwd, false, true>(g, epi, (hipStream_t)stream);
+  return launch_nn<EpiSwiGLUBwd, false, true>(g, epi, stream);
 }
 
 int rv_gemm_nn_lora_pre_bf16(const void* A, long lda, const void* B, long ldb, const void* A2, long lda2, const void* B2,
@@ -539,7 +514,7 @@ int rv_gemm_nn_lora_pre_bf16(const void* A, long lda, const void* B, long ldb, c
   g.pre_thresh16 = d.thresh16;
   g.pre_key = d.key;
   g.pre_inv_keep = d.inv_keep;
-  return launch_nn<EpiStore, false, true>(g, epi_store(C, ldc, nullptr, residual, ldr, RV_ACT_NONE, 1.0f), (hipStream_t)stream);
+  return launch_nn<EpiStore, false, true>(g, epi_store(C, ldc, nullptr, residual, ldr, RV_ACT_NONE, 1.0f), stream);
 }
 
 int rv_gemm_nt_dropout_bf16(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
@@ -569,10 +544,10 @@ int rv_gemm_tn_bf16_splitk(const void* P, long ldp, const void* Q, long ldq, voi
   CHECK(check_align(who, {P, Q, workspace}, 16, "P/Q/workspace"));
   REQ(workspace != nullptr, "workspace of splits*I*J floats required");
   const SplitK s = splitk_chunks(R, splits);
-  if (launch_gemm_tn((const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, R, I, J, EpiStoreF32{workspace, (long)J}, (hipStream_t)stream, s.splits,
+  if (launch_gemm_tn((const bf16_t*)P, ldp, (const bf16_t*)Q, ldq, R, I, J, EpiStoreF32{workspace, (long)J}, stream, s.splits,
                      s.r_chunk, (long)I * J))
     return 1;
-  return launch_splitk_reduce(workspace, s.splits, I, J, alpha, C, ldc, (hipStream_t)stream);
+  return launch_splitk_reduce(workspace, s.splits, I, J, alpha, C, ldc, stream);
 }
 
 int rv_gemm_nt_lora_masks_bf16(const void* X, long ldx, const void* A, long lda, void* T, long ldt, int M, int K, int G,
@@ -593,8 +568,8 @@ int rv_gemm_nt_lora_masks_bf16(const void* X, long ldx, const void* A, long lda,
     constexpr int G_ = decltype(Gc)::value, NST = G_ == 1 ? 3 : 2, LDS = NST * (16384 + G_ * 8192);
     const dim3 grid((M + 127) / 128), block(256);
     const bf16_t *x = (const bf16_t*)X, *a = (const bf16_t*)A;
-    if (dm.thresh16) return launch<lora_masks_fwd_kernel<G_, NST, true>>(LDS, grid, block, (hipStream_t)stream, x, ldx, a, lda, (bf16_t*)T, ldt, M, K, alpha, dm);
-    return launch<lora_masks_fwd_kernel<G_, NST, false>>(LDS, grid, block, (hipStream_t)stream, x, ldx, a, lda, (bf16_t*)T, ldt, M, K, alpha, dm);
+    if (dm.thresh16) return launch<lora_masks_fwd_kernel<G_, NST, true>>(LDS, grid, block, stream, x, ldx, a, lda, (bf16_t*)T, ldt, M, K, alpha, dm);
+    return launch<lora_masks_fwd_kernel<G_, NST, false>>(LDS, grid, block, stream, x, ldx, a, lda, (bf16_t*)T, ldt, M, K, alpha, dm);
   });
 }
 
@@ -619,8 +594,8 @@ int rv_gemm_nt_dropout_masks_bf16(const void* dT, long lddt, const void* AT, lon
     constexpr int G_ = decltype(Gc)::value;
     const dim3 grid(tiles(M, GEMM_BM) * tiles(N, GEMM_BN)), block(GEMM_THREADS);
     const bf16_t *dt = (const bf16_t*)dT, *at = (const bf16_t*)AT, *r = (const bf16_t*)residual;
-    if (dm.thresh16) return launch<lora_masks_dgrad_kernel<G_, true>>(GEMM_LDS_BYTES, grid, block, (hipStream_t)stream, dt, lddt, at, ldat, (bf16_t*)C, ldc, r, ldr, M, N, dm);
-    return launch<lora_masks_dgrad_kernel<G_, false>>(GEMM_LDS_BYTES, grid, block, (hipStream_t)stream, dt, lddt, at, ldat, (bf16_t*)C, ldc, r, ldr, M, N, dm);
+    if (dm.thresh16) return launch<lora_masks_dgrad_kernel<G_, true>>(GEMM_LDS_BYTES, grid, block, stream, dt, lddt, at, ldat, (bf16_t*)C, ldc, r, ldr, M, N, dm);
+    return launch<lora_masks_dgrad_kernel<G_, false>>(GEMM_LDS_BYTES, grid, block, stream, dt, lddt, at, ldat, (bf16_t*)C, ldc, r, ldr, M, N, dm);
   });
 }
 
@@ -642,11 +617,11 @@ int rv_gemm_tn_lora_masks_bf16(const void* dT, long lddt, const void* X, long ld
   const SplitK s = splitk_chunks(R, splits);
   const LoraMasks dm = lora_masks(p, seed0, seed1, seed2);
   const int rc = for_modules(G, [&](auto Gc) {
-    return launch<lora_masks_wgrad_kernel<decltype(Gc)::value>>(0, dim3(tiles(K, LMW_JT), s.splits), dim3(256), (hipStream_t)stream,
+    return launch<lora_masks_wgrad_kernel<decltype(Gc)::value>>(0, dim3(tiles(K, LMW_JT), s.splits), dim3(256), stream,
                                                                (const bf16_t*)dT, lddt, (const bf16_t*)X, ldx, workspace, R, K, s.r_chunk, dm);
   });
   if (rc) return rc;
-  return launch_splitk_reduce(workspace, s.splits, G * 64, K, 1.0f, dA, ldda, (hipStream_t)stream);
+  return launch_splitk_reduce(workspace, s.splits, G * 64, K, 1.0f, dA, ldda, stream);
 }
 
 int rv_gemm_nt_bf16_f32out(const void* A, long lda, const void* B, long ldb, float* C, long ldc, int M, int N, int K,
