@@ -489,6 +489,55 @@ int rv_attn_decode(const void* q, long ldq, const void* kv, long ldkv, int k_col
 int rv_sample_token(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids, float penalty,
                     float temperature, float top_p, const float* u, int* token, float* logp, void* stream);
 
+/* ---- Beam-search decoding (csrc/beam.hip, rv_attn_decode_indexed in csrc/decode.hip; additive, ABI stays 7).  Replaces the decode
+ *      steps of HF GenerationMixin._beam_search behind model.generate(do_sample=False, num_beams=3) in muffin/eval/muffin_vqa.py,
+ *      muffin/eval/llava15_chair.py and chat.py.
+ *
+ * rv_attn_decode_indexed: rv_attn_decode with the sequence's own span given as a ROW TABLE: key t of sequence m is cache row
+ *   pre_off[m] + t for t < pre_len[m], else own_rows[m * ld_rows + (t - pre_len[m])] (int32).  Beams with a common ancestor name the
+ *   same rows; nothing in the cache is copied or reordered when beams are reselected.  Everything else - split, online softmax,
+ *   merge, combine, workspace (rv_attn_decode_workspace_floats), rounding, determinism - is rv_attn_decode's: with the identity
+ *   table own_rows[m][i] = own_off[m] + i the result is the same bits.  cur_own_len: the largest own_len[m] of the call (the
+ *   CALLER's statement), ld_rows >= cur_own_len is checked; inside the kernel own_len[m] is clamped to ld_rows and every table
+ *   entry to [0, kv_rows), kv_rows = rows of the cache: a bad table reads wrong rows, never memory outside the cache or the table.
+ *   The table entries of a batch of four keys are loaded ahead of the K / V loads that depend on them. */
+int rv_attn_decode_indexed(const void* q, long ldq, const void* kv, long ldkv, int kv_rows, int k_col0, int v_col0,
+                           const int* pre_off, const int* pre_len, const int* own_rows, long ld_rows, int cur_own_len,
+                           const int* own_len, void* out, long ldo, float* lse, int M, int H, int hd, int kv_group, float scale,
+                           int n_split, float* workspace, long workspace_floats, void* stream);
+/* rv_beam_topk: per group g of K beams (rows g K .. g K + K - 1 of fp32 logits [G K][ldl], columns [0, V_valid), V_valid <= 65536)
+ *   the 2K best of the K V_valid values  log_softmax(row b)[v] + score[g K + b], sorted descending, as cand_val / cand_parent (b) /
+ *   cand_tok (v), [G][2K] each; lse fp32 [G K] = log sum exp of each row.  log_softmax in fp32 as rv_sample_token: max, sum of
+ *   exp(x - max), log; value = ((x - max) - log Z) + score, one rounding per operation.  Equal values order by the lower flat index
+ *   b * V_valid + v.  Columns >= V_valid are never read.  A beam with score -1e9 (HF's start value of beams 1..K-1) gives finite
+ *   values near -1e9 that lose to every live candidate.  2 K <= V_valid.  Two launches: one workgroup per row keeps the row in
+ *   registers and finds its own top 2K by 2K block arg-max rounds (wave butterfly, then the 16 wave results in wave order), one
+ *   wave per group merges the K lists; every reduction has a fixed order: the same bits on every run.
+ *   workspace: fp32, rv_beam_topk_workspace_floats(G, K) elements (0 for bad arguments), needs no initialisation.  1 <= K <= 8. */
+long rv_beam_topk_workspace_floats(int G, int K);
+int rv_beam_topk(const float* logits, long ldl, const float* score, int G, int K, int V_valid, float* cand_val, int* cand_parent,
+                 int* cand_tok, float* lse, float* workspace, long workspace_floats, void* stream);
+/* rv_beam_step: step j (0-based, of at most T) of GenerationMixin._beam_search (transformers 5.x, do_sample=False,
+ *   early_stopping=False, one EOS id, generation from inputs_embeds: the prompt length counts 0) on the 2K candidates of every
+ *   group, one wave per group.  A candidate "stops" when its token is eos_token_id (-1: none) or when `last` = (j == T - 1).
+ *   - running beams: the K best candidates that do not stop, in order -> run_score / parent / token [G K]; slots left over (every
+ *     candidate stops) take the stopping candidates in order at value + (-1e9);
+ *   - stopping candidates of rank < K join the group's finished set with score value / len_div, len_div = (j + 1) ** length_penalty
+ *     (host-computed); the set keeps the K best (an equal score does not evict); slot s: hyp_tokens [G][K][T] (its j + 1 tokens),
+ *     hyp_len, hyp_score [G K]; n_hyp [G] = slots in use (slots are NOT sorted);
+ *   - done[g] = every candidate stops, or the set is full and run_score[g K] / len_div <= its worst score (with a free slot the
+ *     worst counts -1e9).  A group with done[g] != 0 on entry keeps selecting and advancing but its finished set is frozen;
+ *   - tables, buffer A -> buffer B (the caller swaps): row m = g K + b of hist_b / rows_b = row g K + parent[m] of hist_a / rows_a
+ *     (entries < j) with entry j appended: token[m], and own_base + j * (G K) + m - the cache row the caller writes this token's
+ *     K | V to (step-major).  A and B must not overlap (an in-place gather is a race between beams).  ld_t >= T = the row length.
+ *   force_parent / force_token / force_score (int32, int32, fp32 [G K]; all or none, test hook): the running beams are these
+ *   instead of the selection (parents clamped to [0, K)), the finished set and done are left alone.
+ *   n_hyp and done must be zeroed before step 0.  Everything else is written before it is read. */
+int rv_beam_step(const float* cand_val, const int* cand_parent, const int* cand_tok, int G, int K, int T, int j, int eos_token_id,
+                 float len_div, int last, int own_base, const int* force_parent, const int* force_token, const float* force_score,
+                 float* run_score, int* parent, int* token, const int* hist_a, int* hist_b, const int* rows_a, int* rows_b, long ld_t,
+                 int* hyp_tokens, int* hyp_len, float* hyp_score, int* n_hyp, int* done, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,16 +161,21 @@ __device__ __forceinline__ void ad_unpack8(const uint4 v, float* f) {
 }
 __device__ __forceinline__ float ad_w(float m, float mn) { return m == -INFINITY ? 0.f : exp2f(m - mn); }
 
-template <int G>
+// IDX (rv_attn_decode_indexed): the sequence's own span is a row table, `own_off` = own_rows [M][ld_rows]; an entry is clamped
+// to the cache's rows [0, kv_rows), so a bad table reads wrong rows and never memory outside the cache.
+template <int G, bool IDX>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restrict__ q, long ldq,
                                                           const bf16_t* __restrict__ kv, long ldkv, int k_col0, int v_col0,
                                                           const int* __restrict__ pre_off, const int* __restrict__ pre_len,
                                                           const int* __restrict__ own_off, const int* __restrict__ own_len,
-                                                          int H, int n_split, float scale_log2e, float* __restrict__ ws) {
+                                                          int H, int n_split, float scale_log2e, float* __restrict__ ws,
+                                                          long ld_rows, int kv_rows) {
   __shared__ float sm[4][G][AD_HD + 2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, dsub = lane & 15, ksub = lane >> 4;
   const int g = blockIdx.x / n_split, sp = blockIdx.x % n_split, m = blockIdx.y;
-  const int pl = pre_len[m], po = pre_off[m], oo = own_off[m], T = pl + own_len[m];
+  const int pl = pre_len[m], po = pre_off[m], oo = IDX ? 0 : own_off[m];
+  const int T = pl + (IDX ? min(own_len[m], (int)ld_rows) : own_len[m]);      // IDX: never past the table's row
+  const int* tab = own_off + (long)m * ld_rows;              // IDX only
   const int chunk = (T + n_split - 1) / n_split;
   const int t0 = sp * chunk, t1 = min(T, t0 + chunk);
   float qf[G][8], o[G][8], mx[G], l[G];
@@ -184,12 +189,26 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
   const long kc = (long)k_col0 + (long)g * AD_HD + 8 * dsub, vc = (long)v_col0 + (long)g * AD_HD + 8 * dsub;
   for (int t = t0 + wave * 4 + ksub; t < t1; t += 64) {
     uint4 kr[4], vr[4];
+    if constexpr (IDX) {
+      long row[4];
 #pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int tt = min(t + 16 * b, t1 - 1);                 // a key past the split: re-read its last row, weight 0 below
-      const long row = tt < pl ? (long)po + tt : (long)oo + (tt - pl);
-      kr[b] = *(const uint4*)(kv + row * ldkv + kc);
-      vr[b] = *(const uint4*)(kv + row * ldkv + vc);
+      for (int b = 0; b < 4; ++b) {                           // the batch's table entries first: four loads in flight, then K / V
+        const int tt = min(t + 16 * b, t1 - 1);
+        row[b] = tt < pl ? (long)po + tt : (long)min(max(tab[tt - pl], 0), kv_rows - 1);
+      }
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        kr[b] = *(const uint4*)(kv + row[b] * ldkv + kc);
+        vr[b] = *(const uint4*)(kv + row[b] * ldkv + vc);
+      }
+    } else {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int tt = min(t + 16 * b, t1 - 1);               // a key past the split: re-read its last row, weight 0 below
+        const long row = tt < pl ? (long)po + tt : (long)oo + (tt - pl);
+        kr[b] = *(const uint4*)(kv + row * ldkv + kc);
+        vr[b] = *(const uint4*)(kv + row * ldkv + vc);
+      }
     }
     float s[4][G];
 #pragma unroll
@@ -292,28 +311,30 @@ extern "C" long rv_attn_decode_workspace_floats(int M, int H, int n_split) {
   return (long)M * H * n_split * AD_WS;
 }
 
-extern "C" int rv_attn_decode(const void* q, long ldq, const void* kv, long ldkv, int k_col0, int v_col0, const int* pre_off,
-                              const int* pre_len, const int* own_off, const int* own_len, void* out, long ldo, float* lse,
-                              int M, int H, int hd, int kv_group, float scale, int n_split, float* workspace,
-                              long workspace_floats, void* stream) {
-  RV_REQUIRE(hd == AD_HD, "rv_attn_decode: hd must be 128");
-  RV_REQUIRE(M >= 1 && M <= 65535 && H >= 1, "rv_attn_decode: 1 <= M <= 65535, H >= 1");
-  RV_REQUIRE(kv_group == 1 || kv_group == 2 || kv_group == 4 || kv_group == 8, "rv_attn_decode: kv_group in {1, 2, 4, 8}");
-  RV_REQUIRE(H % kv_group == 0, "rv_attn_decode: kv_group must divide H");
-  RV_REQUIRE(n_split >= 1 && n_split <= 256, "rv_attn_decode: 1 <= n_split <= 256");
-  RV_REQUIRE(q && kv && out && pre_off && pre_len && own_off && own_len && workspace, "rv_attn_decode: NULL buffer");
-  RV_REQUIRE(workspace_floats >= rv_attn_decode_workspace_floats(M, H, n_split),
-             "rv_attn_decode: workspace smaller than rv_attn_decode_workspace_floats(M, H, n_split)");
-  RV_REQUIRE(ldq % 8 == 0 && ldkv % 8 == 0 && k_col0 % 8 == 0 && v_col0 % 8 == 0 && k_col0 >= 0 && v_col0 >= 0,
-             "rv_attn_decode: ldq, ldkv, k_col0, v_col0 must be multiples of 8");
-  RV_REQUIRE(ldq >= (long)H * hd && ldo >= (long)H * hd, "rv_attn_decode: ldq / ldo smaller than H * hd");
-  RV_REQUIRE((((uintptr_t)q | (uintptr_t)kv | (uintptr_t)workspace) & 15) == 0, "rv_attn_decode: q / kv / workspace 16-byte aligned");
+// the argument checks and the two launches that rv_attn_decode and rv_attn_decode_indexed share
+template <bool IDX>
+static int attn_decode_run(const char* who, const void* q, long ldq, const void* kv, long ldkv, int k_col0, int v_col0,
+                           const int* pre_off, const int* pre_len, const int* own, long ld_rows, int kv_rows, const int* own_len,
+                           void* out, long ldo, float* lse, int M, int H, int hd, int kv_group, float scale, int n_split,
+                           float* workspace, long workspace_floats, void* stream) {
+  RV_REQUIRE_AS(who, hd == AD_HD, "hd must be 128");
+  RV_REQUIRE_AS(who, M >= 1 && M <= 65535 && H >= 1, "1 <= M <= 65535, H >= 1");
+  RV_REQUIRE_AS(who, kv_group == 1 || kv_group == 2 || kv_group == 4 || kv_group == 8, "kv_group in {1, 2, 4, 8}");
+  RV_REQUIRE_AS(who, H % kv_group == 0, "kv_group must divide H");
+  RV_REQUIRE_AS(who, n_split >= 1 && n_split <= 256, "1 <= n_split <= 256");
+  RV_REQUIRE_AS(who, q && kv && out && pre_off && pre_len && own && own_len && workspace, "NULL buffer");
+  RV_REQUIRE_AS(who, workspace_floats >= rv_attn_decode_workspace_floats(M, H, n_split),
+                "workspace smaller than rv_attn_decode_workspace_floats(M, H, n_split)");
+  RV_REQUIRE_AS(who, ldq % 8 == 0 && ldkv % 8 == 0 && k_col0 % 8 == 0 && v_col0 % 8 == 0 && k_col0 >= 0 && v_col0 >= 0,
+                "ldq, ldkv, k_col0, v_col0 must be multiples of 8");
+  RV_REQUIRE_AS(who, ldq >= (long)H * hd && ldo >= (long)H * hd, "ldq / ldo smaller than H * hd");
+  RV_REQUIRE_AS(who, (((uintptr_t)q | (uintptr_t)kv | (uintptr_t)workspace) & 15) == 0, "q / kv / workspace 16-byte aligned");
   const int nkv = H / kv_group;
   const dim3 grid(nkv * n_split, M), block(256);
   const float sl2 = scale * 1.4426950408889634f;
-#define AD_LAUNCH(G)                                                                                               \
-  launch<attn_decode_kernel<G>>(0, grid, block, stream, (const bf16_t*)q, ldq, (const bf16_t*)kv, ldkv, k_col0, v_col0, \
-                                pre_off, pre_len, own_off, own_len, H, n_split, sl2, workspace)
+#define AD_LAUNCH(G)                                                                                                         \
+  launch<attn_decode_kernel<G, IDX>>(0, grid, block, stream, (const bf16_t*)q, ldq, (const bf16_t*)kv, ldkv, k_col0, v_col0, \
+                                     pre_off, pre_len, own, own_len, H, n_split, sl2, workspace, ld_rows, kv_rows)
   int rc;
   switch (kv_group) {
     case 1: rc = AD_LAUNCH(1); break;
@@ -324,6 +345,27 @@ extern "C" int rv_attn_decode(const void* q, long ldq, const void* kv, long ldkv
 #undef AD_LAUNCH
   if (rc) return rc;
   return launch<attn_decode_combine_kernel>(0, dim3(H, M), dim3(AD_HD), stream, workspace, n_split, (bf16_t*)out, ldo, lse, H);
+}
+
+extern "C" int rv_attn_decode(const void* q, long ldq, const void* kv, long ldkv, int k_col0, int v_col0, const int* pre_off,
+                              const int* pre_len, const int* own_off, const int* own_len, void* out, long ldo, float* lse,
+                              int M, int H, int hd, int kv_group, float scale, int n_split, float* workspace,
+                              long workspace_floats, void* stream) {
+  return attn_decode_run<false>("rv_attn_decode", q, ldq, kv, ldkv, k_col0, v_col0, pre_off, pre_len, own_off, 0, 0, own_len, out,
+                                ldo, lse, M, H, hd, kv_group, scale, n_split, workspace, workspace_floats, stream);
+}
+
+extern "C" int rv_attn_decode_indexed(const void* q, long ldq, const void* kv, long ldkv, int kv_rows, int k_col0, int v_col0,
+                                      const int* pre_off, const int* pre_len, const int* own_rows, long ld_rows, int cur_own_len,
+                                      const int* own_len, void* out, long ldo, float* lse, int M, int H, int hd, int kv_group,
+                                      float scale, int n_split, float* workspace, long workspace_floats, void* stream) {
+  RV_REQUIRE(kv_rows >= 1, "rv_attn_decode_indexed: kv_rows (rows of the cache) must be >= 1");
+  RV_REQUIRE(cur_own_len >= 0 && ld_rows >= cur_own_len && ld_rows >= 1,
+             "rv_attn_decode_indexed: ld_rows must be >= 1 and >= the current own length");
+  RV_REQUIRE(((uintptr_t)own_rows & 3) == 0, "rv_attn_decode_indexed: own_rows must be 4-byte aligned");
+  return attn_decode_run<true>("rv_attn_decode_indexed", q, ldq, kv, ldkv, k_col0, v_col0, pre_off, pre_len, own_rows, ld_rows,
+                               kv_rows, own_len, out, ldo, lse, M, H, hd, kv_group, scale, n_split, workspace, workspace_floats,
+                               stream);
 }
 
 // ------------------------------------------------------------------ sampler

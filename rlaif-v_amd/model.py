@@ -1124,9 +1124,11 @@ class LlavaDPOModel:
         return self._last_position_logits(plan, images, caches)
 
     def _decode_step(self, tok: torch.Tensor, pos: torch.Tensor, dst: torch.Tensor, spans, caches: List[torch.Tensor],
-                     n_split: int, out: torch.Tensor):
+                     n_split: int, out: torch.Tensor, own_rows: Optional[torch.Tensor] = None, cur_own_len: int = 0):
         """One decode step of at most 64 sequences: token ids ``tok`` at RoPE positions ``pos``, their K | V appended at cache
-        rows ``dst``, attention over ``spans`` (current token included), fp32 logits into ``out`` [M, vocab_padded]."""
+        rows ``dst``, attention over ``spans`` (current token included), fp32 logits into ``out`` [M, vocab_padded].
+        ``own_rows`` (beam search): the sequences' own keys are the rows this int32 [M, T] table names, ``cur_own_len`` of them,
+        and ``spans`` = (pre_off, pre_len, own_len); without it ``spans`` = (pre_off, pre_len, own_off, own_len)."""
         cfg, st = self.cfg, self.store
         d, H, hd, kvd = cfg.hidden, cfg.heads, cfg.head_dim, cfg.kv_dim
         cos, sin = self._rope_cache[1], self._rope_cache[2]
@@ -1142,7 +1144,11 @@ class LlavaDPOModel:
             qkv = ops.gemm_nt_skinny(xn, st.p(f"layers.{i}.wqkv"))
             ops.rope_inplace(qkv, cos, sin, 1, H + cfg.n_kv_heads, hd, pos=pos)           # q heads then k heads
             ops.scatter_rows(qkv[:, d:], dst, caches[i])
-            attn, _ = ops.attn_decode(qkv, caches[i], H, hd, 0, kvd, spans, kv_group=cfg.kv_group, n_split=n_split)
+            if own_rows is None:
+                attn, _ = ops.attn_decode(qkv, caches[i], H, hd, 0, kvd, spans, kv_group=cfg.kv_group, n_split=n_split)
+            else:
+                attn, _ = ops.attn_decode_indexed(qkv, caches[i], H, hd, 0, kvd, spans, own_rows, cur_own_len,
+                                                  kv_group=cfg.kv_group, n_split=n_split)
             if self.resid_fp32:
                 o = ops.gemm_nt_skinny(attn, st.p(f"layers.{i}.wo"))
                 x, xn2, _ = ops.add_rmsnorm_fwd(x, o, st.p(f"layers.{i}.ln2"), cfg.rms_eps)
@@ -1190,7 +1196,7 @@ class LlavaDPOModel:
         if getattr(cfg, "arch", "llava") == "omnilmm" or self._row_splicer() is not None:
             raise NotImplementedError("generate(): OmniLMM (resampler splice) is not supported")
         if num_beams != 1:
-            raise NotImplementedError("generate(): beam search (num_beams > 1) is not supported")
+            raise NotImplementedError("generate(): beam search (num_beams > 1) is not supported here - use beam_search()")
         if cfg.head_dim != 128:
             raise NotImplementedError("generate(): rv_attn_decode needs head_dim 128")
         if len(prompts) != len(images) or len(prompts) == 0:
@@ -1260,6 +1266,99 @@ class LlavaDPOModel:
                         seq = seq[:seq.index(int(eos_token_id)) + 1]
                     out[-1].append(seq)
             return (out, torch.stack(scores)) if return_scores else out
+
+    # ------------------------------------------------------------------ beam-search decoding (the evaluation stage)
+    def beam_search(self, prompts, images, max_new_tokens: int, num_beams: int = 3, eos_token_id: Optional[int] = None,
+                    length_penalty: float = 1.0, return_trace: bool = False, *, _forced=None):
+        """One answer per (image, prompt) the way the reference's evaluation produces it (muffin/eval/muffin_vqa.py,
+        llava15_chair.py, chat.py: ``generate(do_sample=False, num_beams=3, max_new_tokens=)`` from inputs_embeds): HF's
+        GenerationMixin._beam_search with early_stopping=False and one EOS id.  Prefill is ``generate``'s (_prefill); its
+        last-position logits serve the ``num_beams`` beams of a prompt, which share the prompt's cache rows
+        (splice.plan_beam_rows).  A step is ``generate``'s decode step with rv_attn_decode_indexed in place of rv_attn_decode,
+        then rv_beam_topk (the 2K best of log_softmax + beam score per prompt) and rv_beam_step (running beams, finished
+        hypotheses, stop rule, and the per-beam token history and cache-row table for the next step) - all on the device; the
+        loop is a host ``for`` and the done flags are read back every 8 steps.  Step j's K | V go to fresh cache rows; a
+        reselection of beams changes table entries only, no cache row is ever copied or reordered.  A prompt that is done keeps
+        its rows and is decoded on until all are (its finished set is frozen), as in ``generate``.
+        Returns (tokens, scores): tokens[k] = the new token ids of prompt k's best hypothesis (it ends with ``eos_token_id`` if
+        it finished on it), scores[k] = its ``sequences_scores`` = sum of log-probs / length ** length_penalty.
+        ``return_trace`` (tests): a third value, a dict of per-step tensors - ``logits`` [steps, M, vocab] fp32, the device's
+        candidates ``cand_val`` / ``cand_parent`` / ``cand_tok`` [steps, G, 2K], its running beams ``parent`` / ``token`` /
+        ``score`` [steps, M], and ``done`` [steps, G], ``n_hyp`` [steps, G], ``hyp_score`` / ``hyp_len`` [steps, G, K] after each
+        step, plus the final ``hyp_tokens`` [G, K, T].  ``_forced`` (test hook, keyword-only) = (parent, token[, score]), each
+        [steps, M]: follow these beams instead of the device's selection (teacher forcing for beams) for ``steps`` steps; no
+        hypothesis is collected and tokens / scores are None."""
+        cfg = self.cfg
+        if self.lora is not None:
+            raise NotImplementedError("beam_search(): un-merged LoRA adapters are not supported - merge_lora() first")
+        if getattr(cfg, "arch", "llava") == "omnilmm" or self._row_splicer() is not None:
+            raise NotImplementedError("beam_search(): OmniLMM (resampler splice) is not supported")
+        if cfg.head_dim != 128:
+            raise NotImplementedError("beam_search(): rv_attn_decode_indexed needs head_dim 128")
+        if not 1 <= num_beams <= 8:
+            raise NotImplementedError(f"beam_search(): num_beams must be 1..8 (rv_beam_topk), got {num_beams}")
+        if len(prompts) != len(images) or len(prompts) == 0:
+            raise ValueError(f"{len(prompts)} prompts for {len(images)} images")
+        if max_new_tokens < 1:
+            raise ValueError("beam_search(): max_new_tokens must be >= 1")
+        from .splice import plan_beam_rows
+        T, K, G, dev = int(max_new_tokens), int(num_beams), len(prompts), self.device
+        with self._eval_mode():
+            cpu_plan = build_branch_plan([[p] for p in prompts], cfg.n_image_tokens, cfg.model_max_length,
+                                         splicer=None, pad_free=True, packed=False)
+            rows = plan_beam_rows(cpu_plan.row_off.tolist(), cpu_plan.row_len.tolist(), K, T)
+            M = rows.n_seq
+            self._rope(cpu_plan.L + T)
+            n_split = min(8, max(1, (cpu_plan.L + T) // 256))       # generate()'s rule: a function of the lengths only
+            caches = [torch.empty(rows.n_rows, 2 * cfg.kv_dim, dtype=BF16, device=dev) for _ in range(cfg.layers)]
+            logits = self._prefill(prompts, images, caches)[rows.prompt_of.long().to(dev)]       # [M, vocab_padded]
+            pre_off = rows.pre_off.to(dev)
+            rows = replace(rows, pre_len=rows.pre_len.to(dev), seq_idx=rows.seq_idx.to(dev))
+            state = ops.BeamState(G, K, T, rows.own_base, dev)
+            forced, n_max = None, T
+            if _forced is not None:
+                forced = [torch.as_tensor(t).to(dev) for t in _forced]
+                if len(forced) == 2:
+                    forced.append(torch.zeros(forced[0].shape, dtype=torch.float32, device=dev))
+                n_max = int(forced[0].shape[0])
+                if len(forced) != 3 or not 1 <= n_max <= T or any(tuple(t.shape) != (n_max, M) for t in forced):
+                    raise ValueError(f"beam_search(): _forced = (parent, token[, score]), each [steps <= {T}, {M}]")
+                forced = [forced[0].to(torch.int32).contiguous(), forced[1].to(torch.int32).contiguous(),
+                          forced[2].to(torch.float32).contiguous()]
+            keys = ("logits", "cand_val", "cand_parent", "cand_tok", "parent", "token", "score", "done", "n_hyp", "hyp_score",
+                    "hyp_len")
+            trace = {k: [] for k in keys}
+            for j in range(n_max):
+                if j > 0:
+                    logits = torch.empty(M, cfg.vocab_padded, dtype=torch.float32, device=dev)
+                    pos, dst, own_len = rows.step(j - 1)      # feeds token j - 1, chosen last step
+                    for c0, c1 in rows.chunks:
+                        self._decode_step(state.token[c0:c1], pos[c0:c1], dst[c0:c1], (pre_off[c0:c1], rows.pre_len[c0:c1],
+                                          own_len[c0:c1]), caches, n_split, logits[c0:c1], own_rows=state.own_rows[c0:c1],
+                                          cur_own_len=j)
+                cand = ops.beam_topk(logits, state.run_score, G, K, cfg.vocab)[:3]
+                ops.beam_step(state, cand, j, eos_token_id, length_penalty,
+                              forced=None if forced is None else (forced[0][j], forced[1][j], forced[2][j]))
+                if return_trace:
+                    for k, t in zip(keys, (logits[:, :cfg.vocab], *cand, state.parent, state.token, state.run_score, state.done,
+                                           state.n_hyp, state.hyp_score, state.hyp_len)):
+                        trace[k].append(t.clone())
+                if eos_token_id is not None and forced is None and j % 8 == 7 and bool(state.done.all()):
+                    break                                      # the one read-back of the loop, every 8 steps
+            tokens = scores = None
+            if forced is None:
+                n_hyp, hyp_len = state.n_hyp.cpu().tolist(), state.hyp_len.cpu().tolist()
+                hyp_score, hyp_tokens = state.hyp_score.cpu(), state.hyp_tokens.cpu()
+                tokens, scores = [], []
+                for g in range(G):                             # the best finished hypothesis wins (the lower slot among equals)
+                    best = int(torch.argmax(hyp_score[g, :n_hyp[g]]))
+                    tokens.append(hyp_tokens[g, best, :hyp_len[g][best]].tolist())
+                    scores.append(float(hyp_score[g, best]))
+            if not return_trace:
+                return tokens, scores
+            out = {k: torch.stack(v) for k, v in trace.items()}
+            out["hyp_tokens"] = state.hyp_tokens.clone()
+            return tokens, scores, out
 
     # ------------------------------------------------------------------ backward
     def backward(self, out: StepOutput, coef: torch.Tensor):

@@ -862,6 +862,121 @@ def sample_token(logits: torch.Tensor, n_rows: int, v_valid: int, u: Optional[to
     return token, logp
 
 
+# ------------------------------------------------------------------------------------- beam search (csrc/beam.hip)
+def attn_decode_indexed(q: torch.Tensor, kv: torch.Tensor, H: int, hd: int, k_col0: int, v_col0: int, spans, own_rows: torch.Tensor,
+                        cur_own_len: int, kv_group: int = 1, n_split: int = 1, out: Optional[torch.Tensor] = None,
+                        want_lse: bool = False, workspace: Optional[torch.Tensor] = None):
+    """``attn_decode`` with the sequence's own span given as a row table (rv_attn_decode_indexed): ``spans`` = (pre_off, pre_len,
+    own_len) int32 [M], ``own_rows`` int32 [M, ld]: key t >= pre_len[m] of sequence m is cache row own_rows[m, t - pre_len[m]].
+    ``cur_own_len``: the largest own_len of the call (<= ld).  Every entry below own_len must name a row of ``kv``.
+    Returns (out [M, H*hd] bf16, lse [M, H] fp32 or None)."""
+    _chk2d(q, "q"), _chk2d(kv, "kv")
+    M = q.shape[0]
+    if q.shape[1] < H * hd:
+        raise ValueError(f"attn_decode_indexed: q has {q.shape[1]} columns, needs H * hd = {H * hd}")
+    if H % kv_group != 0:
+        raise ValueError("attn_decode_indexed: kv_group must divide H")
+    n_kv_cols = (H // kv_group) * hd
+    if not (0 <= k_col0 and k_col0 + n_kv_cols <= kv.shape[1] and 0 <= v_col0 and v_col0 + n_kv_cols <= kv.shape[1]):
+        raise ValueError(f"attn_decode_indexed: K / V head columns do not fit the cache's {kv.shape[1]} columns")
+    if len(spans) != 3:
+        raise ValueError("attn_decode_indexed: spans = (pre_off, pre_len, own_len)")
+    for name, t in zip(("pre_off", "pre_len", "own_len"), spans):
+        if t.dtype != torch.int32 or t.numel() != M or not t.is_contiguous() or t.device != q.device:
+            raise ValueError(f"attn_decode_indexed: {name} must be contiguous int32 [{M}] on {q.device}")
+    if (own_rows.dim() != 2 or own_rows.dtype != torch.int32 or own_rows.shape[0] != M or own_rows.stride(1) != 1
+            or own_rows.device != q.device):
+        raise ValueError(f"attn_decode_indexed: own_rows must be int32 [{M}, ld] with unit column stride on {q.device}")
+    if not 0 <= cur_own_len <= own_rows.shape[1]:
+        raise ValueError(f"attn_decode_indexed: cur_own_len {cur_own_len} does not fit the table's {own_rows.shape[1]} columns")
+    if out is None:
+        out = torch.empty(M, H * hd, dtype=BF16, device=q.device)
+    _chk2d(out, "out")
+    if out.shape[0] != M or out.shape[1] < H * hd:
+        raise ValueError(f"attn_decode_indexed: out is {tuple(out.shape)}, needs [{M}, >= {H * hd}]")
+    if workspace is None:
+        workspace = attn_decode_workspace(q.device, M, H, n_split)
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != q.device:
+        raise ValueError("attn_decode_indexed: workspace must be a contiguous fp32 tensor on q's device")
+    lse = torch.empty(M, H, dtype=torch.float32, device=q.device) if want_lse else None
+    hip.call("rv_attn_decode_indexed", q, q.stride(0), kv, kv.stride(0), kv.shape[0], int(k_col0), int(v_col0), spans[0], spans[1],
+             own_rows, own_rows.stride(0), int(cur_own_len), spans[2], out, out.stride(0), lse, M, H, hd, int(kv_group),
+             1.0 / math.sqrt(hd), int(n_split), workspace, workspace.numel())
+    return out, lse
+
+
+def beam_topk(logits: torch.Tensor, score: torch.Tensor, n_groups: int, num_beams: int, v_valid: int):
+    """Per group of ``num_beams`` rows of fp32 ``logits`` [>= G K, ld] the 2K best of log_softmax(row)[v] + score[row] over the
+    columns [0, v_valid), sorted descending, equal values by the lower beam * v_valid + v (rv_beam_topk).
+    Returns (value fp32, parent int32, token int32: [G, 2K] each; lse fp32 [G K])."""
+    G, K = int(n_groups), int(num_beams)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1 or not logits.is_cuda:
+        raise ValueError("beam_topk: logits must be a 2-D fp32 CUDA tensor with unit column stride")
+    if not 1 <= K <= 8:
+        raise ValueError(f"beam_topk: 1 <= num_beams <= 8, got {K}")
+    if not (G >= 1 and G * K <= logits.shape[0] and 2 * K <= v_valid <= logits.shape[1]):
+        raise ValueError(f"beam_topk: {G} x {K} rows, {v_valid} columns do not fit logits {tuple(logits.shape)}")
+    dev = logits.device
+    if score.dtype != torch.float32 or score.numel() != G * K or not score.is_contiguous() or score.device != dev:
+        raise ValueError(f"beam_topk: score must be contiguous fp32 [{G * K}] on the logits' device")
+    val = torch.empty(G, 2 * K, dtype=torch.float32, device=dev)
+    par = torch.empty(G, 2 * K, dtype=torch.int32, device=dev)
+    tok = torch.empty(G, 2 * K, dtype=torch.int32, device=dev)
+    lse = torch.empty(G * K, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(hip.lib().lib.rv_beam_topk_workspace_floats(G, K)), dtype=torch.float32, device=dev)
+    hip.call("rv_beam_topk", logits, logits.stride(0), score, G, K, int(v_valid), val, par, tok, lse, ws, ws.numel())
+    return val, par, tok, lse
+
+
+class BeamState:
+    """The device state of a beam search over G groups of K beams and at most T steps (rv_beam_step's buffers): running scores
+    (beam 0 live, the others at HF's -1e9), the ping-pong token history and cache-row table, the finished-hypothesis set."""
+
+    def __init__(self, n_groups: int, num_beams: int, max_steps: int, own_base: int, device):
+        G, K, T = int(n_groups), int(num_beams), int(max_steps)
+        if not (G >= 1 and 1 <= K <= 8 and T >= 1 and own_base >= 0):
+            raise ValueError("BeamState: n_groups >= 1, 1 <= num_beams <= 8, max_steps >= 1, own_base >= 0")
+        M = G * K
+        i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=device)        # noqa: E731
+        self.G, self.K, self.T, self.own_base = G, K, T, int(own_base)
+        self.run_score = torch.full((G, K), -1.0e9, dtype=torch.float32, device=device)
+        self.run_score[:, 0] = 0.0
+        self.run_score = self.run_score.view(-1)
+        self.parent, self.token = i32(M), i32(M)
+        self.hist, self.hist_next = i32(M, T), i32(M, T)
+        self.own_rows, self.own_rows_next = i32(M, T), i32(M, T)
+        self.hyp_tokens, self.hyp_len, self.n_hyp, self.done = i32(G, K, T), i32(G, K), i32(G), i32(G)
+        self.hyp_score = torch.full((G, K), -1.0e9, dtype=torch.float32, device=device)
+
+
+def beam_step(state: BeamState, cand, j: int, eos_token_id: Optional[int] = None, length_penalty: float = 1.0, forced=None):
+    """Step ``j`` of the beam search on the candidates ``cand`` = (value, parent, token) of ``beam_topk`` (rv_beam_step): new
+    running beams (state.run_score / parent / token), finished hypotheses, done flags, and the token history and cache-row
+    table advanced into the other buffer, which becomes the current one.  ``forced`` = (parent, token, score) [G K]: follow
+    these beams instead of the selection (test hook: the finished set and the done flags stay as they are)."""
+    G, K, T = state.G, state.K, state.T
+    if not 0 <= j < T:
+        raise ValueError(f"beam_step: step {j} outside [0, {T})")
+    val, par, tok = cand
+    dev = state.run_score.device
+    for name, t, dt in (("value", val, torch.float32), ("parent", par, torch.int32), ("token", tok, torch.int32)):
+        if t.dtype != dt or t.numel() != G * 2 * K or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"beam_step: candidate {name} must be contiguous {dt} [{G}, {2 * K}] on {dev}")
+    fp = ft = fs = None
+    if forced is not None:
+        fp, ft, fs = forced
+        for name, t, dt in (("parent", fp, torch.int32), ("token", ft, torch.int32), ("score", fs, torch.float32)):
+            if t.dtype != dt or t.numel() != G * K or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"beam_step: forced {name} must be contiguous {dt} [{G * K}] on {dev}")
+    hip.call("rv_beam_step", val, par, tok, G, K, T, int(j), -1 if eos_token_id is None else int(eos_token_id),
+             float((j + 1) ** float(length_penalty)), int(j == T - 1), state.own_base, fp, ft, fs, state.run_score, state.parent,
+             state.token, state.hist, state.hist_next, state.own_rows, state.own_rows_next, T, state.hyp_tokens, state.hyp_len,
+             state.hyp_score, state.n_hyp, state.done)
+    state.hist, state.hist_next = state.hist_next, state.hist
+    state.own_rows, state.own_rows_next = state.own_rows_next, state.own_rows
+    return state
+
+
 def gemm_auto_variant(M: int, N: int) -> int:
     """The NT GEMM kernel the library picks for an [M, N] output when no variant is forced (gemm.hip dispatch: the 256 x 256
     tile kernel from 192 tiles on)."""

@@ -572,3 +572,49 @@ def plan_decode_rows(row_off: Sequence[int], row_len: Sequence[int], repeat: int
                       pre_off=i32(off)[prompt_of.long()], pre_len=i32(ln)[prompt_of.long()],
                       own_off=n_prefill + torch.arange(n_seq, dtype=torch.int32) * max_new,
                       chunks=[(c, min(c + max_rows, n_seq)) for c in range(0, n_seq, max_rows)])
+
+
+@dataclass
+class BeamRows:
+    """Cache rows of ``LlavaDPOModel.beam_search``, the beam counterpart of ``DecodeRows``: sequence m = prompt * num_beams + beam;
+    the beams of a prompt share its prompt span.  No beam owns rows: step j writes the K | V of sequence m to the fresh row
+    ``own_base + j * n_seq + m`` (step-major) and a per-beam row table (rv_beam_step) names the rows of its ancestry, so a
+    reselection of beams moves table entries, never cache rows."""
+    n_seq: int
+    n_rows: int                # rows of one layer's cache
+    num_beams: int
+    prompt_of: torch.Tensor    # int32 [n_seq] the prompt (= prefill row) a sequence continues
+    pre_off: torch.Tensor      # int32 [n_seq] first cache row of its prompt
+    pre_len: torch.Tensor      # int32 [n_seq] tokens of the spliced prompt
+    own_base: int              # first cache row behind the prompts
+    seq_idx: torch.Tensor      # int32 [n_seq] 0 .. n_seq - 1
+    chunks: List[Tuple[int, int]]   # [c0, c1) sequence ranges of at most ``max_rows`` rows, whole groups only
+
+    def step(self, j: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Decode step j (it feeds generated token j): (RoPE position of that token, the cache row its K | V go to, own_len
+        INCLUDING it), int32 [n_seq] each."""
+        return self.pre_len + j, self.seq_idx + (self.own_base + j * self.n_seq), torch.full_like(self.pre_len, j + 1)
+
+
+def plan_beam_rows(row_off: Sequence[int], row_len: Sequence[int], num_beams: int, max_new: int, max_rows: int = 64) -> BeamRows:
+    """``row_off`` / ``row_len``: the pad-free prefill rows of the prompts (build_branch_plan(packed=False)), in prompt order."""
+    if num_beams < 1 or max_new < 1 or max_rows < 1:
+        raise ValueError("plan_beam_rows: num_beams, max_new and max_rows must be >= 1")
+    if num_beams > max_rows:
+        raise ValueError("plan_beam_rows: a chunk of max_rows rows must hold a whole group of num_beams beams")
+    if len(row_off) != len(row_len) or len(row_off) == 0:
+        raise ValueError("plan_beam_rows: one (row_off, row_len) pair per prompt, at least one prompt")
+    off, ln = [int(x) for x in row_off], [int(x) for x in row_len]
+    if any(n < 1 for n in ln) or any(o < 0 for o in off):
+        raise ValueError("plan_beam_rows: empty prompt or negative row offset")
+    n_prefill = max(o + n for o, n in zip(off, ln))
+    n_seq = len(off) * num_beams
+    if n_prefill + n_seq * max_new > 2 ** 31 - 1:
+        raise ValueError("plan_beam_rows: the cache rows do not fit int32")
+    prompt_of = torch.arange(len(off), dtype=torch.int32).repeat_interleave(num_beams)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32)                   # noqa: E731
+    per = (max_rows // num_beams) * num_beams
+    return BeamRows(n_seq=n_seq, n_rows=n_prefill + n_seq * max_new, num_beams=num_beams, prompt_of=prompt_of,
+                    pre_off=i32(off)[prompt_of.long()], pre_len=i32(ln)[prompt_of.long()], own_base=n_prefill,
+                    seq_idx=torch.arange(n_seq, dtype=torch.int32),
+                    chunks=[(c, min(c + per, n_seq)) for c in range(0, n_seq, per)])
