@@ -488,6 +488,26 @@ int rv_attn_decode(const void* q, long ldq, const void* kv, long ldkv, int k_col
  *   reproduced.  One workgroup per row, fixed reduction order; logits are read only, inside [0, V_valid) of rows < M. */
 int rv_sample_token(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids, float penalty,
                     float temperature, float top_p, const float* u, int* token, float* logp, void* stream);
+/* rv_sample_token_wide (csrc/sample_wide.hip; additive, ABI stays 7): rv_sample_token for 1 <= V_valid <= 262144 (Llama-3: 128256
+ *   ids) - the same steps 1 - 5, greedy rule, token / logp and argument order, followed by a workspace.  The row is not held in
+ *   registers but streamed (it is L2 / MALL-resident behind the LM head): one workgroup of 16 waves per row, wave w owns the ids
+ *   [w SEG, (w + 1) SEG), SEG = ceil(V_valid / 16) rounded up to a multiple of 256, in tiles of 256 (lane l: ids 4 l .. 4 l + 3), so
+ *   vocabulary order is (wave, tile, lane, element).  Passes over the row: max / arg-max, Z, and when sampling with top_p < 1 ONE
+ *   pass that writes out, in vocabulary order, the tokens of probability > (1 - top_p) / (2 V_valid) - the others are dropped at
+ *   any threshold, their mass is summed - then step 3's bisection over that list, the kept mass, and the draw.  A wave's first 512
+ *   candidates stay in LDS, further ones go to its SEG floats of the workspace.
+ *   DETERMINISTIC: every sum is lane-accumulate over the tiles, wave butterfly, 16 wave results in wave order; no floating-point
+ *   atomic; the running sum of the draw is in vocabulary order.  A row's token and logp are a function of that row, u[m] and its
+ *   seen ids alone (not of M).  The sums run in another order than rv_sample_token's, so at V_valid <= 65536 the two agree in
+ *   distribution and in every draw farther than the fp32 summation error from a CDF boundary, not bit for bit in logp.
+ *   CONTAINED: reads [0, V_valid) of rows < M only, for any ldl >= V_valid and any 4-byte-aligned row start (16-byte loads only
+ *   when logits is 16-byte aligned and ldl % 4 == 0); writes token, logp and the workspace only.
+ *   workspace: fp32, rv_sample_token_wide_workspace_floats(M, V_valid) = M * 16 * SEG elements (0 for bad arguments), needs no
+ *   initialisation, holds nothing between calls. */
+long rv_sample_token_wide_workspace_floats(int M, int V_valid);
+int rv_sample_token_wide(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids, float penalty,
+                         float temperature, float top_p, const float* u, int* token, float* logp, float* workspace,
+                         long workspace_floats, void* stream);
 
 /* ---- Beam-search decoding (csrc/beam.hip, rv_attn_decode_indexed in csrc/decode.hip; additive, ABI stays 7).  Replaces the decode
  *      steps of HF GenerationMixin._beam_search behind model.generate(do_sample=False, num_beams=3) in muffin/eval/muffin_vqa.py,

@@ -35,6 +35,16 @@ def hf_config_dict(cfg) -> Dict:
             "rlaifv_im_start_token": cfg.im_start_token, "rlaifv_im_end_token": cfg.im_end_token,
             "tokenizer_model_max_length": cfg.model_max_length,
         }
+    if getattr(cfg, "arch", "llava") == "text":
+        return {
+            "architectures": ["LlamaForCausalLM"], "model_type": "llama",
+            "hidden_size": cfg.hidden, "intermediate_size": cfg.ffn, "num_hidden_layers": cfg.layers,
+            "num_attention_heads": cfg.heads, "num_key_value_heads": cfg.n_kv_heads, "vocab_size": cfg.vocab,
+            "rms_norm_eps": cfg.rms_eps, "rope_theta": cfg.rope_theta, "rope_scaling": None,
+            "max_position_embeddings": cfg.model_max_length, "pad_token_id": cfg.pad_token_id, "hidden_act": "silu",
+            "torch_dtype": "bfloat16", "tie_word_embeddings": False, "use_cache": True,
+            "attention_bias": False, "mlp_bias": False,
+        }
     return {
         "architectures": ["LlavaLlamaForCausalLM"], "model_type": "llava_llama",
         "hidden_size": cfg.hidden, "intermediate_size": cfg.ffn, "num_hidden_layers": cfg.layers,
@@ -63,6 +73,24 @@ def config_from_hf(d: Dict, **overrides):
                   model_max_length=d.get("tokenizer_model_max_length", 2048), pad_token_id=d.get("pad_token_id") or 0)
         kw.update(overrides)
         return OmniLMMConfig(**kw)
+    if d.get("model_type") == "llama":
+        # a plain HF LlamaForCausalLM (Llama-3-8B and its fine-tunes): the text-only model of the claim-splitting stage
+        from .textlm import TextLMConfig
+        if d.get("rope_scaling") is not None:
+            raise NotImplementedError(f"config.json: rope_scaling {d['rope_scaling']!r} is not supported (Llama-3.1 style RoPE "
+                                      "scaling); only rope_scaling: null")
+        if d.get("tie_word_embeddings", False):
+            raise NotImplementedError("config.json: tie_word_embeddings: true is not supported (the LM head is its own tensor)")
+        if d.get("attention_bias", False) or d.get("mlp_bias", False):
+            raise NotImplementedError("config.json: attention_bias / mlp_bias are not supported")
+        if d.get("head_dim") not in (None, d["hidden_size"] // d["num_attention_heads"]):
+            raise NotImplementedError("config.json: head_dim must be hidden_size / num_attention_heads")
+        kw = dict(hidden=d["hidden_size"], layers=d["num_hidden_layers"], heads=d["num_attention_heads"],
+                  kv_heads=d.get("num_key_value_heads", d["num_attention_heads"]), ffn=d["intermediate_size"],
+                  vocab=d["vocab_size"], rms_eps=d.get("rms_norm_eps", 1e-5), rope_theta=d.get("rope_theta", 10000.0),
+                  model_max_length=d.get("max_position_embeddings", 8192), pad_token_id=d.get("pad_token_id") or 0)
+        kw.update(overrides)
+        return TextLMConfig(**kw)
     kw = dict(hidden=d["hidden_size"], layers=d["num_hidden_layers"], heads=d["num_attention_heads"],
               ffn=d["intermediate_size"], vocab=d["vocab_size"], rms_eps=d.get("rms_norm_eps", 1e-5),
               rope_theta=d.get("rope_theta", 10000.0), clip_hidden=d.get("mm_hidden_size", 1024),
@@ -204,6 +232,13 @@ def from_pretrained(ckpt_dir: str, device="cuda:0", with_optimizer: bool = True,
             tower = EvaTower(EvaConfig(width=cfg.vision_width), device=device)
             tower.load_state_dict(sd, prefix="model.vision_tower.")
             model.set_vision_tower(tower)
+        return model
+    if getattr(cfg, "arch", "llava") == "text":
+        # HF LlamaForCausalLM (model.layers.N.*, model.embed_tokens, model.norm, lm_head): inference only, whatever the caller's
+        # with_optimizer default says; LoRA on a text model is refused by name
+        from .textlm import TextLMModel
+        model = TextLMModel(cfg, device=device, with_optimizer=False, lora=lora)
+        model.load_state_dict(sd)
         return model
     model = LlavaDPOModel(cfg, device=device, with_optimizer=with_optimizer, lora=lora)
     model.load_state_dict(sd)

@@ -29,7 +29,8 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 import torch
 
 from . import ops
-from .splice import SplicePlan, build_branch_plan, build_packed_plan, build_splice_plan
+from .splice import (IMAGE_TOKEN_INDEX, SplicePlan, build_branch_plan, build_packed_plan, build_splice_plan, cut_behind_eos,
+                     eos_id_set)
 
 BF16 = torch.bfloat16
 VT = "model.vision_tower.vision_tower.vision_model."
@@ -199,9 +200,17 @@ class ParamStore:
         norms: List[Entry] = [("model.norm.weight", (d,), False)]
         for i in reversed(range(cfg.layers)):
             norms += [(f"layers.{i}.ln2", (d,), False), (f"layers.{i}.ln1", (d,), False)]
-        if lora is None:
+        text_only = getattr(cfg, "arch", "llava") == "text"
+        if text_only:
+            # a text-only language model (textlm.py) is inference-only: nothing trainable, so no gradient or optimizer slot
+            if lora is not None or with_optimizer:
+                raise NotImplementedError("a text-only model (TextLMConfig) cannot be trained: build it with with_optimizer=False "
+                                          "and without LoRA")
+            frozen: List[Entry] = base_w + norms
+            decay, nodecay = [], []
+        elif lora is None:
             # full fine-tune: everything trainable, laid out in backward-completion order
-            frozen: List[Entry] = []
+            frozen = []
             decay = base_w + proj_w
             nodecay = norms + proj_b
         else:
@@ -250,7 +259,9 @@ class ParamStore:
         self.flat_pT = torch.zeros(toff, dtype=BF16, device=device)
         # gradient buckets for data parallelism: contiguous slices of flat_g in the order backward finishes them
         self.buckets: Dict[str, Tuple[int, int]] = {}
-        if lora is None:
+        if text_only:
+            pass
+        elif lora is None:
             self.buckets["lm_head"] = self.grad_range("lm_head.weight", "lm_head.weight")
             for i in reversed(range(cfg.layers)):
                 self.buckets[f"layer{i}"] = self.grad_range(f"layers.{i}.wdown", f"layers.{i}.wqkv")
@@ -1167,7 +1178,7 @@ class LlavaDPOModel:
         ops.gemm_nt_skinny(h, st.p("lm_head.weight"), out=out, out_f32=True)
 
     def generate(self, prompts, images, max_new_tokens: int, repeat: int = 1, temperature: float = 0.0, top_p: float = 1.0,
-                 repetition_penalty: float = 1.0, eos_token_id: Optional[int] = None,
+                 repetition_penalty: float = 1.0, eos_token_id=None,
                  generator: Optional[torch.Generator] = None, return_scores: bool = False, num_beams: int = 1, *,
                  _uniforms: Optional[torch.Tensor] = None, _forced_tokens: Optional[torch.Tensor] = None):
         """The sampling branch of the AI-feedback stage (muffin/llava15_gen_data.py:335-357: ``generate(do_sample=True,
@@ -1188,6 +1199,9 @@ class LlavaDPOModel:
         exists to refuse beam search by name.  Test hooks, keyword-only: ``_uniforms`` (fp32 [max_new_tokens, n_seq]) plants
         the uniforms; ``_forced_tokens`` (int32 [n_seq, max_new_tokens]) feeds given tokens instead of the sampled ones
         (teacher forcing).
+        ``eos_token_id``: an int, or a sequence of ints (HF's ``eos_token_id=[eos, <|eot_id|>]``): a sequence is finished by the
+        first id of the set.  A text-only model (textlm.py) takes ``images=None`` and prompts without the image placeholder.
+        The sampler is ops.sampler_for(vocab): rv_sample_token up to 65536 ids, rv_sample_token_wide above.
         Returns tokens[k][r] = the new token ids of sample r of prompt k, cut behind the first ``eos_token_id``; with
         ``return_scores`` (test only) also the fp32 logits [steps, n_seq, vocab] every step sampled from."""
         cfg, st = self.cfg, self.store
@@ -1199,10 +1213,22 @@ class LlavaDPOModel:
             raise NotImplementedError("generate(): beam search (num_beams > 1) is not supported here - use beam_search()")
         if cfg.head_dim != 128:
             raise NotImplementedError("generate(): rv_attn_decode needs head_dim 128")
-        if len(prompts) != len(images) or len(prompts) == 0:
+        text_only = getattr(cfg, "arch", "llava") == "text"
+        if text_only:
+            if images is not None:
+                raise ValueError("generate(): a text-only model (TextLMConfig) takes images=None")
+            if len(prompts) == 0:
+                raise ValueError("generate(): no prompts")
+            if any(bool((torch.as_tensor(p) == IMAGE_TOKEN_INDEX).any()) for p in prompts):
+                raise ValueError("generate(): a prompt of a text-only model (TextLMConfig) holds the image placeholder")
+        elif images is None:
+            raise ValueError(f"generate(): images=None needs a text-only model (TextLMConfig), this one is '{cfg.arch}'")
+        elif len(prompts) != len(images) or len(prompts) == 0:
             raise ValueError(f"{len(prompts)} prompts for {len(images)} images")
         if max_new_tokens < 1 or repeat < 1:
             raise ValueError("generate(): max_new_tokens and repeat must be >= 1")
+        eos_ids = eos_id_set(eos_token_id)
+        sampler, wide = ops.sampler_for(cfg.vocab)
         from .splice import plan_decode_rows
         T, dev = int(max_new_tokens), self.device
         with self._eval_mode():
@@ -1232,6 +1258,10 @@ class LlavaDPOModel:
                 seen = (torch.arange(M + 1, dtype=torch.int32, device=dev) * T, seen_ids.view(-1))
             tokens = torch.zeros(M, T, dtype=torch.int32, device=dev)
             done = torch.zeros(M, dtype=torch.bool, device=dev)
+            eos_t = torch.tensor(eos_ids, dtype=torch.int32, device=dev) if eos_ids is not None and len(eos_ids) > 1 else None
+            extra = {}
+            if wide:
+                extra["workspace"] = torch.empty(ops.sample_token_wide_workspace_floats(M, cfg.vocab), dtype=torch.float32, device=dev)
             scores = []
             n_steps = 0
             for j in range(T):
@@ -1242,8 +1272,8 @@ class LlavaDPOModel:
                         self._decode_step(tokens[c0:c1, j - 1].contiguous(), pos[c0:c1], dst[c0:c1],
                                           (pre_off[c0:c1], pre_len[c0:c1], own_off[c0:c1], own_len[c0:c1]), caches, n_split,
                                           logits[c0:c1])
-                tok, _ = ops.sample_token(logits, M, cfg.vocab, uniforms[j] if sampling else None, float(temperature),
-                                          float(top_p), seen=seen, penalty=float(repetition_penalty))
+                tok, _ = sampler(logits, M, cfg.vocab, uniforms[j] if sampling else None, float(temperature),
+                                 float(top_p), seen=seen, penalty=float(repetition_penalty), **extra)
                 if forced_tokens is not None:
                     tok = forced_tokens[:, j]
                 tokens[:, j] = tok
@@ -1252,8 +1282,8 @@ class LlavaDPOModel:
                 if return_scores:
                     scores.append(logits[:, :cfg.vocab].clone())
                 n_steps = j + 1
-                if eos_token_id is not None:
-                    done |= tok == int(eos_token_id)
+                if eos_ids is not None:
+                    done |= (tok == eos_ids[0]) if eos_t is None else torch.isin(tok, eos_t)
                     if j % 8 == 7 and bool(done.all()):            # the one read-back of the loop, every 8 steps
                         break
             host = tokens[:, :n_steps].cpu().tolist()
@@ -1261,10 +1291,7 @@ class LlavaDPOModel:
             for k in range(len(prompts)):
                 out.append([])
                 for r in range(repeat):
-                    seq = host[k * repeat + r]
-                    if eos_token_id is not None and int(eos_token_id) in seq:
-                        seq = seq[:seq.index(int(eos_token_id)) + 1]
-                    out[-1].append(seq)
+                    out[-1].append(cut_behind_eos(host[k * repeat + r], eos_ids))
             return (out, torch.stack(scores)) if return_scores else out
 
     # ------------------------------------------------------------------ beam-search decoding (the evaluation stage)

@@ -862,6 +862,70 @@ def sample_token(logits: torch.Tensor, n_rows: int, v_valid: int, u: Optional[to
     return token, logp
 
 
+def sample_token_wide(logits: torch.Tensor, n_rows: int, v_valid: int, u: Optional[torch.Tensor], temperature: float = 0.0,
+                      top_p: float = 1.0, seen: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, penalty: float = 1.0,
+                      workspace: Optional[torch.Tensor] = None):
+    """``sample_token`` for vocabularies up to 262144 ids (rv_sample_token_wide): the same distribution, draw and return values
+    with the row streamed instead of held in registers.  ``workspace``: fp32, at least ``sample_token_wide_workspace_floats``
+    elements (allocated here when None)."""
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1 or not logits.is_cuda:
+        raise ValueError("sample_token_wide: logits must be a 2-D fp32 CUDA tensor with unit column stride")
+    if not (0 < n_rows <= logits.shape[0] and 0 < v_valid <= logits.shape[1]):
+        raise ValueError(f"sample_token_wide: {n_rows} rows x {v_valid} columns do not fit logits {tuple(logits.shape)}")
+    if v_valid > SAMPLE_WIDE_MAX_V:
+        raise ValueError(f"sample_token_wide: v_valid {v_valid} > {SAMPLE_WIDE_MAX_V}")
+    if not temperature >= 0.0:
+        raise ValueError("sample_token_wide: temperature must be >= 0 (0 = greedy)")
+    if not top_p > 0.0:
+        raise ValueError("sample_token_wide: top_p must be > 0")
+    if not penalty > 0.0:
+        raise ValueError("sample_token_wide: the repetition penalty must be positive")
+    dev = logits.device
+    if u is None:
+        if temperature != 0.0:
+            raise ValueError("sample_token_wide: sampling (temperature > 0) needs the uniforms u")
+    elif u.dtype != torch.float32 or u.numel() != n_rows or not u.is_contiguous() or u.device != dev:
+        raise ValueError(f"sample_token_wide: u must be contiguous fp32 [{n_rows}] on the logits' device")
+    seen_off = seen_ids = None
+    if seen is not None and penalty != 1.0:
+        seen_off, seen_ids = seen
+        for name, t in (("seen_off", seen_off), ("seen_ids", seen_ids)):
+            if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"sample_token_wide: {name} must be contiguous int32 on the logits' device")
+        if seen_off.numel() != n_rows + 1:
+            raise ValueError(f"sample_token_wide: seen_off needs {n_rows + 1} entries")
+        if seen_ids.numel() == 0:
+            seen_off = seen_ids = None
+    need = sample_token_wide_workspace_floats(n_rows, v_valid)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float32, device=dev)
+    elif workspace.dtype != torch.float32 or not workspace.is_contiguous() or workspace.device != dev or workspace.numel() < need:
+        raise ValueError(f"sample_token_wide: workspace must be a contiguous fp32 tensor of >= {need} elements on the logits' device")
+    token = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    logp = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    hip.call("rv_sample_token_wide", logits, logits.stride(0), n_rows, v_valid, seen_off, seen_ids, float(penalty),
+             float(temperature), float(top_p), u, token, logp, workspace, workspace.numel())
+    return token, logp
+
+
+SAMPLE_REG_MAX_V = 65536        # rv_sample_token holds the row in registers
+SAMPLE_WIDE_MAX_V = 262144      # rv_sample_token_wide streams it
+
+
+def sample_token_wide_workspace_floats(n_rows: int, v_valid: int) -> int:
+    return int(hip.lib().lib.rv_sample_token_wide_workspace_floats(int(n_rows), int(v_valid)))
+
+
+def sampler_for(v_valid: int):
+    """The sampler generate() uses for a vocabulary: rv_sample_token up to 65536 ids (existing models keep their exact bits),
+    rv_sample_token_wide above.  -> (function, needs_workspace)"""
+    if v_valid <= SAMPLE_REG_MAX_V:
+        return sample_token, False
+    if v_valid <= SAMPLE_WIDE_MAX_V:
+        return sample_token_wide, True
+    raise ValueError(f"no sampler for a vocabulary of {v_valid} ids (rv_sample_token_wide: V_valid <= {SAMPLE_WIDE_MAX_V})")
+
+
 # ------------------------------------------------------------------------------------- beam search (csrc/beam.hip)
 def attn_decode_indexed(q: torch.Tensor, kv: torch.Tensor, H: int, hd: int, k_col0: int, v_col0: int, spans, own_rows: torch.Tensor,
                         cur_own_len: int, kv_group: int = 1, n_split: int = 1, out: Optional[torch.Tensor] = None,

@@ -20,6 +20,7 @@ Two layouts:
 """
 from __future__ import annotations
 
+import numbers
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
@@ -618,3 +619,33 @@ def plan_beam_rows(row_off: Sequence[int], row_len: Sequence[int], num_beams: in
                     pre_off=i32(off)[prompt_of.long()], pre_len=i32(ln)[prompt_of.long()], own_base=n_prefill,
                     seq_idx=torch.arange(n_seq, dtype=torch.int32),
                     chunks=[(c, min(c + per, n_seq)) for c in range(0, n_seq, per)])
+
+
+# ------------------------------------------------------------------------------------------------ end-of-sequence ids
+def eos_id_set(eos_token_id) -> Optional[Tuple[int, ...]]:
+    """``generate(eos_token_id=...)`` as a tuple of distinct ids in the caller's order: None stays None, an int is a set of one,
+    a sequence of ints (HF's ``eos_token_id=[eos, <|eot_id|>]``) is taken as it is.  Anything else raises ValueError."""
+    if eos_token_id is None:
+        return None
+    if isinstance(eos_token_id, bool):
+        raise ValueError("eos_token_id must be an int or a sequence of ints")
+    if isinstance(eos_token_id, numbers.Integral):
+        return (int(eos_token_id),)
+    if torch.is_tensor(eos_token_id):
+        eos_token_id = eos_token_id.reshape(-1).tolist()
+    try:
+        ids = [i for i in eos_token_id]
+    except TypeError:
+        raise ValueError("eos_token_id must be an int or a sequence of ints") from None
+    if len(ids) == 0 or any(isinstance(i, bool) or not isinstance(i, numbers.Integral) for i in ids):
+        raise ValueError("eos_token_id must be an int or a non-empty sequence of ints")
+    return tuple(dict.fromkeys(int(i) for i in ids))
+
+
+def cut_behind_eos(seq: List[int], eos_ids: Optional[Tuple[int, ...]]) -> List[int]:
+    """The generated ids up to and including the first one that is in ``eos_ids`` (all of them when there is none)."""
+    if eos_ids:
+        for n, t in enumerate(seq):
+            if t in eos_ids:
+                return seq[:n + 1]
+    return seq
