@@ -256,7 +256,9 @@ int rv_row_coef(const float* coef, const int* seq_of_row, const float* weight, f
  *   K/V tiles are staged by LDS-DMA and transposed on the fly (ds_read_b64_tr_b16): no side copies. */
 /*   seg_sh / seg_e1 (int32 [S], both NULL = plain causal): packed preference pairs.  Row s holds
  *   [shared prefix | chosen branch | rejected branch]; queries at index >= seg_e1[s] (rejected branch) do not attend
- *   keys in [seg_sh[s], seg_e1[s]) (the chosen branch): the image / prompt prefix is computed ONCE per pair. */
+ *   keys in [seg_sh[s], seg_e1[s]) (the chosen branch): the image / prompt prefix is computed ONCE per pair.
+ *   With causal = 0 the window still applies: queries at index >= seg_e1[s] do not see the keys [seg_sh[s], seg_e1[s]), every other
+ *   (query, key) pair of the row is visible (tests/test_accuracy_gpu.py, layout full-window-L200, forward and backward). */
 /*   row_off / row_len (int32 [S], both NULL = S rectangular rows of L tokens; ABI 6): PAD-FREE rows.  Sequence s occupies token
  *   rows [row_off[s], row_off[s] + row_len[s]) of qkv / out (1 <= row_len[s] <= L); the reference right-pads every row to the batch
  *   maximum (llava/model/llava_arch.py:305-313) and SURVEY 8a property (i) makes skipping those pads exact.  L stays the MAXIMUM row

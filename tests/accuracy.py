@@ -531,9 +531,11 @@ def rope_bwd_val(val: Val, doc: torch.Tensor, cos: torch.Tensor, sin: torch.Tens
     return Val(torch.cat([ac + bs, bc - as_], 1), torch.cat([e1, e2], 1)), torch.cat([d1, d2], 1)
 
 
-def emulate_attn_fwd(q, k, v, allowed, scale, online: bool = True, tile: int = 64):
+def emulate_attn_fwd(q, k, v, allowed, scale, online: bool = True, tile: int = 64, rescale_last: bool = True):
     """CPU emulation of the forward kernel's arithmetic: fp32 throughout, exp2 of fma(S, c, -m), P rounded to bf16 for the PV product,
-    the row sum from the unrounded p; online (64-key tiles, running maximum, rescale) or plain (one pass).  Returns (out bf16, lse)."""
+    the row sum from the unrounded p; online (64-key tiles, running maximum, rescale) or plain (one pass).  Returns (out bf16, lse).
+    rescale_last = False is a PLANTED DEFECT (tests/test_accuracy_helper.py): the last tile moves the maximum but o and l are not
+    rescaled by alpha."""
     LOG2E, LN2 = torch.tensor(1.4426950408889634, dtype=F32), torch.tensor(0.6931471805599453, dtype=F32)
     qf, kf, vf = q.float(), k.float(), v.float()
     c = torch.tensor(scale, dtype=F32) * LOG2E
@@ -548,6 +550,8 @@ def emulate_attn_fwd(q, k, v, allowed, scale, online: bool = True, tile: int = 6
         St = S[:, k0:k1]
         m_new = torch.maximum(m, St.max(-1, keepdim=True).values * c)
         alpha = torch.where(torch.isinf(m_new), torch.ones_like(m), torch.exp2(m - m_new))
+        if not rescale_last and k0 > 0 and k1 == Lk:
+            alpha = torch.ones_like(m)
         neg_m = torch.where(torch.isinf(m_new), torch.zeros_like(m), -m_new)
         p = torch.exp2(St * c + neg_m)
         o = o * alpha + p.to(BF).float() @ vf[k0:k1]
@@ -573,6 +577,18 @@ def causal_allowed(Lq: int, Lk: int, device="cpu", seg=None) -> torch.Tensor:
     """causal mask; seg = (sh, e1): queries at index >= e1 do not see the keys [sh, e1) (packed preference pairs)"""
     i, j = torch.arange(Lq, device=device)[:, None], torch.arange(Lk, device=device)[None, :]
     ok = j <= i
+    if seg is not None:
+        ok = ok & ~((i >= seg[1]) & (j >= seg[0]) & (j < seg[1]))
+    return ok
+
+
+def full_allowed(Lq: int, Lk: int, device="cpu", seg=None) -> torch.Tensor:
+    """non-causal mask (rv_attn_fwd / rv_attn_bwd with causal = 0): every query sees every key; seg = (sh, e1): the window still
+    applies - queries at index >= e1 do not see the keys [sh, e1).  Together with causal_allowed this is the kernels' documented
+    predicate (attention.hip, "Element masks"): hidden(q, key) <=> key >= L || (CAUSAL && key > q) || (q >= e1 && sh <= key < e1).
+    Lq != Lk: the first Lq queries of a row of Lk keys (the Resampler's live queries)."""
+    i, j = torch.arange(Lq, device=device)[:, None], torch.arange(Lk, device=device)[None, :]
+    ok = torch.ones(Lq, Lk, dtype=torch.bool, device=device)
     if seg is not None:
         ok = ok & ~((i >= seg[1]) & (j >= seg[0]) & (j < seg[1]))
     return ok

@@ -987,10 +987,45 @@ def c_next_token_scores(dev):
 
 
 # =========================================================================================== attention
-def _attn_layout(dev, L, hd, G, lens=None, seed=0):
+ATTN_LAYOUTS = {"L1": dict(L=1), "L65": dict(L=65), "L200": dict(L=200), "packed-L200": dict(L=200, seg=([40, 0], [120, 64])),
+                "pad-free-130-77": dict(L=130, lens=[130, 77])}
+CAUSAL_LAYOUTS = list(ATTN_LAYOUTS)
+# causal = 0 (attn_fwd2_kernel<64 / 128, false>, attn_fwd3_kernel<false>, attn_bwd_dq2 / dkv3 / dkv5_kernel<false>): one pass per
+# workgroup, an unpaired grid, kv_end = L and t_begin = 0 - every query meets the ragged last key tile, the only masked one.  The
+# smallest shapes that reach each path.  hds / G128: where the discrimination cap (accuracy.check) admits the layout - at L = 257 with
+# head dim 128 and ONE kv head, and at L = 577 with head dim 128, median E / ulp of `out` passes 1/8 (tests/test_accuracy_helper.py
+# runs every admitted combination through the CPU emulation and prints the figures).
+FULL_LAYOUTS = {
+    "full-L1": dict(L=1),                                         # a single key and a single query
+    "full-L65": dict(L=65),                                       # one full key tile + a one-key tail, for every query
+    "full-L200": dict(L=200),                                     # two 128-query blocks; the ragged fourth key tile is seen by all rows
+    "full-L257": dict(L=257, G128=(1,)),                          # three 128-query blocks (odd, unpaired grid); 256 + 1 for fwd3's 256-query blocks
+    "full-pad-free-130-77": dict(L=130, lens=[130, 77]),          # row_off / row_len with causal = 0 (varlen_done without pairing)
+    "full-window-L200": dict(L=200, seg=([40, 0], [120, 64])),    # the window under causal = 0: queries >= e1 do not see [sh, e1)
+    "full-L577": dict(L=577, hds=(64,)),                          # the CLIP tower's own length: 4 blocks + 65
+    # the OmniLMM Resampler: nq live queries against all L keys; the query rows >= nq are zero and so is their dO.  Reference and
+    # bound are built from the nq live queries only (Lq = 64, Lk = 200): a dead row may contribute NOTHING to dK / dV
+    "resampler-L200-nq64": dict(L=200, nq=64, hds=(128,)),
+}
+for _c in FULL_LAYOUTS.values():
+    _c["causal"] = False
+ATTN_LAYOUTS.update(FULL_LAYOUTS)
+
+
+def full_layout_cases(**axes):
+    """grid(**axes, layout = the non-causal layouts) without the combinations the cap does not admit (FULL_LAYOUTS)"""
+    out = []
+    for cid, kw in grid(**axes, layout=list(FULL_LAYOUTS)):
+        c, hd = FULL_LAYOUTS[kw["layout"]], kw.get("hd", 128)
+        if hd in c.get("hds", (64, 128)) and (hd != 128 or kw["G"] in c.get("G128", (1, 2))):
+            out.append((cid, kw))
+    return out
+
+
+def _attn_layout(dev, L, hd, G, lens=None, seed=0, nq=None):
     """S = 2, H = 2 (kv_group G: H / G key / value heads) with the input rows of accuracy.spiked_attention_rows, laid out as qkv
     [tokens][q heads | k heads | v heads].  lens: pad-free rows (sequence s has lens[s] <= L tokens, 3 / 5 token rows of gap in front
-    of the sequences): returns (qkv, q, k, v, starts, lens)"""
+    of the sequences); nq: the query rows >= nq of every sequence are zero (the Resampler): returns (qkv, q, k, v, starts, lens)"""
     S, H, Hkv = 2, 2, 2 // G
     q, k, v = A.spiked_attention_rows(S, L, H, hd, seed=seed, device=dev, kv_heads=Hkv)
     lens = lens or [L, L]
@@ -1002,16 +1037,17 @@ def _attn_layout(dev, L, hd, G, lens=None, seed=0):
         qkv[a:a + n, :H * hd] = q[s_, :, :n].transpose(0, 1).reshape(n, H * hd)
         qkv[a:a + n, H * hd:(H + Hkv) * hd] = k[s_, :, :n].transpose(0, 1).reshape(n, Hkv * hd)
         qkv[a:a + n, (H + Hkv) * hd:] = v[s_, :, :n].transpose(0, 1).reshape(n, Hkv * hd)
+        if nq is not None:
+            qkv[a + nq:a + n, :H * hd] = 0
     return qkv, q, k, v, starts, lens
 
 
-ATTN_LAYOUTS = {"L1": dict(L=1), "L65": dict(L=65), "L200": dict(L=200), "packed-L200": dict(L=200, seg=([40, 0], [120, 64])),
-                "pad-free-130-77": dict(L=130, lens=[130, 77])}
-
-
-def _allowed(c, s_, n, dev):
+def _allowed(c, s_, n, dev, nq=None):
+    """the mask of sequence s_ (n tokens) as the reference sees it: [nq or n queries][n keys]"""
     seg = (c["seg"][0][s_], c["seg"][1][s_]) if "seg" in c else None
-    return A.causal_allowed(n, n, dev, seg=seg)
+    if c.get("causal", True):
+        return A.causal_allowed(n, n, dev, seg=seg)
+    return A.full_allowed(nq or n, n, dev, seg=seg)
 
 
 def _attn_call_args(c, dev, starts, lens):
@@ -1021,33 +1057,35 @@ def _attn_call_args(c, dev, starts, lens):
 
 
 def _check_attn_fwd(c, dev, hd, G, out, lse, q, k, v, starts, lens, what):
-    """one check per output tensor: all sequences and heads of the case"""
+    """one check per output tensor: all sequences and heads of the case (the live queries of a Resampler layout)"""
     H, scale = 2, 1.0 / math.sqrt(hd)
     go, ro, eo, do_, gl, rl, el = [], [], [], [], [], [], []
     for s_ in range(2):
         n, a = lens[s_], starts[s_]
-        ok = _allowed(c, s_, n, dev)
+        nq = c.get("nq", n)
+        ok = _allowed(c, s_, n, dev, nq)
         for h in range(H):
-            ov, doc, lv = A.attn_fwd_bound(q[s_, h, :n], k[s_, h // G, :n], v[s_, h // G, :n], ok, scale)
-            go.append(out[a:a + n, h * hd:(h + 1) * hd]), ro.append(ov.v), eo.append(ov.e), do_.append(doc)
-            gl.append(lse[s_, h, :n]), rl.append(lv.v), el.append(lv.e)
-    chk(torch.cat(go), Val(torch.cat(ro), torch.cat(eo)), f"{what} out", doc=torch.cat(do_))
-    chk(torch.cat(gl), Val(torch.cat(rl), torch.cat(el)), f"{what} lse")
+            ov, doc, lv = A.attn_fwd_bound(q[s_, h, :nq], k[s_, h // G, :n], v[s_, h // G, :n], ok, scale)
+            go.append(out[a:a + nq, h * hd:(h + 1) * hd]), ro.append(ov.v), eo.append(ov.e), do_.append(doc)
+            gl.append(lse[s_, h, :nq]), rl.append(lv.v), el.append(lv.e)
+    return (chk(torch.cat(go), Val(torch.cat(ro), torch.cat(eo)), f"{what} out", doc=torch.cat(do_)),
+            chk(torch.cat(gl), Val(torch.cat(rl), torch.cat(el)), f"{what} lse"))
 
 
-@case(*grid(version=[2, 3], hd=[64, 128], G=[1, 2], layout=list(ATTN_LAYOUTS)))
+@case(*grid(version=[2, 3], hd=[64, 128], G=[1, 2], layout=CAUSAL_LAYOUTS),
+      *full_layout_cases(version=[2, 3], hd=[64, 128], G=[1, 2]))
 def c_attn_fwd(dev, version, hd, G, layout):
     """rv_attn_fwd, both forward kernels of head dim 128 (rv_set_attn_fwd_version; at head dim 64 there is one kernel and the knob
-    must not matter): bounds and their derivation in accuracy.attn_fwd_bound, first passed by its CPU emulation
+    must not matter), causal and full: bounds and their derivation in accuracy.attn_fwd_bound, first passed by its CPU emulation
     (test_accuracy_helper.py)"""
     from rlaif_v_amd import ops
     c = ATTN_LAYOUTS[layout]
     L = c["L"]
     call("rv_set_attn_fwd_version", version)
-    qkv, q, k, v, starts, lens = _attn_layout(dev, L, hd, G, c.get("lens"))
+    qkv, q, k, v, starts, lens = _attn_layout(dev, L, hd, G, c.get("lens"), nq=c.get("nq"))
     seg, rows = _attn_call_args(c, dev, starts, lens)
     H, Hkv = 2, 2 // G
-    out, lse = ops.attn_fwd(qkv, 2, L, H, hd, True, 0, H * hd, (H + Hkv) * hd, seg=seg, kv_group=G, rows=rows)
+    out, lse = ops.attn_fwd(qkv, 2, L, H, hd, c.get("causal", True), 0, H * hd, (H + Hkv) * hd, seg=seg, kv_group=G, rows=rows)
     _check_attn_fwd(c, dev, hd, G, out, lse, q, k, v, starts, lens, f"rv_attn_fwd (version {version}, hd {hd}, kv_group {G}, {layout})")
 
 
@@ -1068,27 +1106,23 @@ def c_attn_fwd_branches(dev, hd, G):
     _check_attn_fwd(c, dev, hd, G, out, lse, q, k, v, starts, lens, f"rv_attn_fwd_branches (hd {hd}, kv_group {G})")
 
 
-@case(*grid(dkv=[3, 5], rope=[False, True], G=[1, 2], layout=list(ATTN_LAYOUTS)))
-def c_attn_bwd(dev, dkv, rope, G, layout):
-    """rv_attn_bwd (head dim 128), both dK/dV kernels, with and without the fused inverse RoPE, on the forward kernel's O and lse
-    (exact operands of this call): accuracy.attn_bwd_bound / rope_bwd_val, first passed by their CPU emulation.  A key / value head
-    sums the terms of its kv_group query heads in the same fp32 accumulators; the cap is measured against ulp + doc (accuracy.check)"""
-    from rlaif_v_amd import ops
-    c = ATTN_LAYOUTS[layout]
-    L, hd, H, Hkv = c["L"], 128, 2, 2 // G
+def _attn_bwd_dO(c, dev, ntok, starts, lens, H=2, hd=128):
+    """dO of a backward case; the rows of a Resampler layout's dead queries are zero"""
+    dO = rnd(ntok, H * hd, seed=5, dev=dev, scale=0.5)
+    if "nq" in c:
+        for a, n in zip(starts, lens):
+            dO[a + c["nq"]:a + n] = 0
+    return dO
+
+
+def _check_attn_bwd(c, dev, G, dqkv, dO, O, lse, q, k, v, starts, lens, what, rope=None):
+    """one check per gradient: all sequences and heads of the case.  A key / value head sums the terms of its kv_group query heads in
+    the same fp32 accumulators.  rope = (cos, sin, pos) of the fused inverse rotation.  A Resampler layout (nq): the reference has the nq
+    live queries only, over all keys - no term from a dead row - and dQ of the dead rows must be +0 bit for bit (dS = P (dP - delta) with
+    dO = 0 is P * (0 - 0) whatever P is)"""
+    hd, H, Hkv = 128, 2, 2 // G
     scale = 1.0 / math.sqrt(hd)
-    call("rv_set_attn_dkv_version", dkv)
-    qkv, q, k, v, starts, lens = _attn_layout(dev, L, hd, G, c.get("lens"), seed=1)
-    seg, rows = _attn_call_args(c, dev, starts, lens)
     k0, v0 = H * hd, (H + Hkv) * hd
-    O, lse = ops.attn_fwd(qkv, 2, L, H, hd, True, 0, k0, v0, seg=seg, kv_group=G, rows=rows)
-    dO = rnd(qkv.shape[0], H * hd, seed=5, dev=dev, scale=0.5)
-    rp = None
-    if rope:
-        cos, sin = ops.rope_tables(4096, hd, 10000.0, dev)
-        pos = ((torch.arange(qkv.shape[0], dtype=I32) * 53 + 7) % 4096).to(dev)
-        rp = (cos, sin, pos)
-    dqkv = ops.attn_bwd(qkv, O, dO, lse, 2, L, H, hd, True, 0, k0, v0, seg=seg, kv_group=G, rope=rp, rows=rows)
     acc = {n_: ([], [], [], []) for n_ in ("dQ", "dK", "dV")}
 
     def put(name, got, val, doc):
@@ -1096,16 +1130,17 @@ def c_attn_bwd(dev, dkv, rope, G, layout):
             lst.append(x)
     for s_ in range(2):
         n, a = lens[s_], starts[s_]
-        ok = _allowed(c, s_, n, dev)
-        cs = (cos[pos[a:a + n].long()].double(), sin[pos[a:a + n].long()].double()) if rope else None
+        nq = c.get("nq", n)
+        ok = _allowed(c, s_, n, dev, nq)
+        cs = (rope[0][rope[2][a:a + n].long()].double(), rope[1][rope[2][a:a + n].long()].double()) if rope else None
         per_kv = {}
         for h in range(H):
-            res = A.attn_bwd_bound(q[s_, h, :n], k[s_, h // G, :n], v[s_, h // G, :n], dO[a:a + n, h * hd:(h + 1) * hd],
-                                   O[a:a + n, h * hd:(h + 1) * hd], lse[s_, h, :n], ok, scale)
+            res = A.attn_bwd_bound(q[s_, h, :nq], k[s_, h // G, :n], v[s_, h // G, :n], dO[a:a + nq, h * hd:(h + 1) * hd],
+                                   O[a:a + nq, h * hd:(h + 1) * hd], lse[s_, h, :nq], ok, scale)
             val, doc = res["dQ"]
             if rope:
                 val, doc = A.rope_bwd_val(val, doc, *cs)
-            put("dQ", dqkv[a:a + n, h * hd:(h + 1) * hd], val, doc)
+            put("dQ", dqkv[a:a + nq, h * hd:(h + 1) * hd], val, doc)
             for name in ("dK", "dV"):
                 val, doc = res[name]
                 if (h // G, name) in per_kv:
@@ -1117,9 +1152,37 @@ def c_attn_bwd(dev, dkv, rope, G, layout):
                 val, doc = A.rope_bwd_val(val, doc, *cs)
             c0 = (k0 if name == "dK" else v0) + hk * hd
             put(name, dqkv[a:a + n, c0:c0 + hd], val, doc)
-    what = f"rv_attn_bwd (dkv {dkv}, rope {rope}, kv_group {G}, {layout})"
-    for name, (got, vv, ee, doc) in acc.items():
-        A.check(torch.cat(got), torch.cat(vv), torch.cat(ee), BF, f"{what} {name}", doc=torch.cat(doc), cap_unit="ulp+doc")
+        if nq < n:
+            dead = dqkv[a + nq:a + n, :H * hd].contiguous()
+            A.check_bits(dead, torch.zeros_like(dead), f"{what} dQ of the dead query rows")
+    return {name: A.check(torch.cat(got), torch.cat(vv), torch.cat(ee), BF, f"{what} {name}", doc=torch.cat(doc), cap_unit="ulp+doc")
+            for name, (got, vv, ee, doc) in acc.items()}
+
+
+@case(*grid(dkv=[3, 5], rope=[False, True], G=[1, 2], layout=CAUSAL_LAYOUTS),
+      *full_layout_cases(dkv=[3, 5], rope=[False], G=[1, 2]))
+def c_attn_bwd(dev, dkv, rope, G, layout):
+    """rv_attn_bwd (head dim 128), both dK/dV kernels, causal (with and without the fused inverse RoPE) and full, on the forward
+    kernel's O and lse (exact operands of this call): accuracy.attn_bwd_bound / rope_bwd_val, first passed by their CPU emulation.
+    The cap is measured against ulp + doc (accuracy.check)"""
+    from rlaif_v_amd import ops
+    c = ATTN_LAYOUTS[layout]
+    L, hd, H, Hkv = c["L"], 128, 2, 2 // G
+    causal = c.get("causal", True)
+    call("rv_set_attn_dkv_version", dkv)
+    qkv, q, k, v, starts, lens = _attn_layout(dev, L, hd, G, c.get("lens"), seed=1, nq=c.get("nq"))
+    seg, rows = _attn_call_args(c, dev, starts, lens)
+    k0, v0 = H * hd, (H + Hkv) * hd
+    O, lse = ops.attn_fwd(qkv, 2, L, H, hd, causal, 0, k0, v0, seg=seg, kv_group=G, rows=rows)
+    dO = _attn_bwd_dO(c, dev, qkv.shape[0], starts, lens)
+    rp = None
+    if rope:
+        cos, sin = ops.rope_tables(4096, hd, 10000.0, dev)
+        pos = ((torch.arange(qkv.shape[0], dtype=I32) * 53 + 7) % 4096).to(dev)
+        rp = (cos, sin, pos)
+    dqkv = ops.attn_bwd(qkv, O, dO, lse, 2, L, H, hd, causal, 0, k0, v0, seg=seg, kv_group=G, rope=rp, rows=rows)
+    _check_attn_bwd(c, dev, G, dqkv, dO, O, lse, q, k, v, starts, lens, f"rv_attn_bwd (dkv {dkv}, rope {rope}, kv_group {G}, {layout})",
+                    rope=rp)
 
 
 @pytest.mark.parametrize("fn,kw", CASES)

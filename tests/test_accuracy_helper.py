@@ -294,13 +294,34 @@ def test_adamw_honest_passes_and_eps_inside_sqrt_fails():
 
 
 # ------------------------------------------------------------------------------------------------------ attention
-def attn_case(L, hd, seed=0, kvh=2):
-    """[(q, k, v, allowed)] for the four input rows of spiked_attention_rows, causal; the last one also as a packed pair"""
+def attn_case(L, hd, seed=0, kvh=2, mask="causal"):
+    """[(q, k, v, allowed)] for the four input rows of spiked_attention_rows; the last one also as a packed pair.  mask: "causal";
+    "full" = every query sees every key (causal = 0), the packed window [40, 120) still hidden from the queries >= 120; "resampler" =
+    the first 64 queries against all L keys (Lq = 64, Lk = L: the OmniLMM Resampler's live queries)"""
     q, k, v = A.spiked_attention_rows(2, L, 2, hd, seed=seed, kv_heads=kvh)
-    out = [(q[s, h], k[s, h * kvh // 2], v[s, h * kvh // 2], A.causal_allowed(L, L)) for s in range(2) for h in range(2)]
-    if L > 100:
-        out.append((q[0, 1], k[0, kvh - 1], v[0, kvh - 1], A.causal_allowed(L, L, seg=(40, 120))))
+    Lq = 64 if mask == "resampler" else L
+    allowed = A.causal_allowed if mask == "causal" else A.full_allowed
+    out = [(q[s, h, :Lq], k[s, h * kvh // 2], v[s, h * kvh // 2], allowed(Lq, L)) for s in range(2) for h in range(2)]
+    if L > 100 and mask != "resampler":
+        out.append((q[0, 1], k[0, kvh - 1], v[0, kvh - 1], allowed(L, L, seg=(40, 120))))
     return out
+
+
+def attn_masks(L, hd=128):
+    """the masks an emulation test runs at this shape: the non-causal ones next to the causal one, the Resampler shape at L = 200"""
+    return ("causal", "full") + (("resampler",) if (L, hd) == (200, 128) else ())
+
+
+def test_full_allowed_is_the_documented_mask():
+    """hidden(q, key) <=> key >= L || (CAUSAL && key > q) || (q >= e1 && sh <= key < e1), element by element, for both mask builders"""
+    L, sh, e1 = 9, 2, 5
+    for causal, fn in ((True, A.causal_allowed), (False, A.full_allowed)):
+        for seg in (None, (sh, e1), (0, 0), (3, 3)):
+            s0, s1 = seg or (0, 0)
+            want = torch.tensor([[not ((causal and key > q) or (q >= s1 and s0 <= key < s1)) for key in range(L)] for q in range(L)])
+            assert torch.equal(fn(L, L, seg=seg), want), (causal, seg)
+    assert torch.equal(A.full_allowed(4, L, seg=(sh, e1)), A.full_allowed(L, L, seg=(sh, e1))[:4])        # Lq != Lk: the first Lq queries
+    assert bool(A.full_allowed(64, 200).all()) and A.full_allowed(64, 200).shape == (64, 200)
 
 
 @pytest.mark.parametrize("kvh", [2, 1])
@@ -335,14 +356,50 @@ def test_attention_builder_delivers_its_row_kinds(L, hd, kvh):
 @pytest.mark.parametrize("L,hd", [(1, 128), (65, 128), (200, 128), (65, 64), (200, 64)])
 def test_attention_forward_emulation_within_bound(L, hd, online, kvh):
     scale = 1.0 / math.sqrt(hd)
-    outs, docs, lses, got_o, got_l = [], [], [], [], []
-    for q, k, v, ok in attn_case(L, hd, kvh=kvh):     # one check per output tensor: the row kinds are rows of one case
-        out, doc, lse = A.attn_fwd_bound(q, k, v, ok, scale)
-        o, l = A.emulate_attn_fwd(q, k, v, ok, scale, online=online)
-        outs.append(out), docs.append(doc), lses.append(lse), got_o.append(o), got_l.append(l)
-    cat = lambda vals: Val(torch.cat([x.v for x in vals]), torch.cat([x.e for x in vals]))       # noqa: E731
-    assert passes("out", torch.cat(got_o), cat(outs), BF, doc=torch.cat(docs))["ratio"] <= 1.0
-    assert passes("lse", torch.cat(got_l), cat(lses), F32)["ratio"] <= 1.0
+    for mask in attn_masks(L, hd):
+        outs, docs, lses, got_o, got_l = [], [], [], [], []
+        for q, k, v, ok in attn_case(L, hd, kvh=kvh, mask=mask):     # one check per output tensor: the row kinds are rows of one case
+            out, doc, lse = A.attn_fwd_bound(q, k, v, ok, scale)
+            o, l = A.emulate_attn_fwd(q, k, v, ok, scale, online=online)
+            outs.append(out), docs.append(doc), lses.append(lse), got_o.append(o), got_l.append(l)
+        assert passes(f"out ({mask})", torch.cat(got_o), cat_vals(outs), BF, doc=torch.cat(docs))["ratio"] <= 1.0
+        assert passes(f"lse ({mask})", torch.cat(got_l), cat_vals(lses), F32)["ratio"] <= 1.0
+
+
+def cat_vals(vals):
+    return Val(torch.cat([x.v for x in vals]), torch.cat([x.e for x in vals]))
+
+
+def full_mask_bound(hd, kvh, L=200):
+    """(cases, out Val, doc, lse Val) of the all-true mask (with its packed-window case) at L = 200: what a defective emulation is held to"""
+    scale = 1.0 / math.sqrt(hd)
+    cases = attn_case(L, hd, kvh=kvh, mask="full")
+    b = [A.attn_fwd_bound(q, k, v, ok, scale) for q, k, v, ok in cases]
+    return cases, cat_vals([x[0] for x in b]), torch.cat([x[1] for x in b]), cat_vals([x[2] for x in b])
+
+
+@pytest.mark.parametrize("kvh", [2, 1])
+@pytest.mark.parametrize("hd", [64, 128])
+@pytest.mark.parametrize("defect", ["tail-keys-dropped", "causal-mask-applied", "final-rescale-skipped"])
+def test_attention_noncausal_defects_fail(defect, hd, kvh):
+    """what the non-causal GPU cases must be able to see, at L = 200 (three full key tiles and a ragged one of 8 keys): an emulation
+    that leaves out the keys of the last partial tile (k >= 64 * (Lk // 64)), one that applies the causal mask when the full one was
+    asked for, and one whose last tile moves the running maximum without rescaling o and l.  The honest emulation passes the same
+    bound (test_attention_forward_emulation_within_bound)"""
+    L = 200
+    scale = 1.0 / math.sqrt(hd)
+    cases, out, doc, lse = full_mask_bound(hd, kvh, L)
+    got_o, got_l = [], []
+    for q, k, v, ok in cases:
+        if defect == "tail-keys-dropped":
+            o, l = A.emulate_attn_fwd(q, k, v, ok & (torch.arange(L)[None, :] < 64 * (L // 64)), scale)
+        elif defect == "causal-mask-applied":
+            o, l = A.emulate_attn_fwd(q, k, v, ok & A.causal_allowed(L, L), scale)
+        else:
+            o, l = A.emulate_attn_fwd(q, k, v, ok, scale, rescale_last=False)
+        got_o.append(o), got_l.append(l)
+    fails("out", torch.cat(got_o), out, BF, doc=doc)
+    fails("lse", torch.cat(got_l), lse, F32)
 
 
 def test_attention_denominator_from_rounded_p_fails():
@@ -364,23 +421,98 @@ def test_attention_denominator_from_rounded_p_fails():
 def test_attention_backward_emulation_within_bound(L, rope, kvh):
     hd = 128
     fr = (torch.arange(L, dtype=F32)[:, None] * 37 + 5) / (10000.0 ** (torch.arange(0, hd, 2, dtype=F32) / hd))[None, :]
-    cos, sin = fr.cos(), fr.sin()
     scale = 1.0 / math.sqrt(hd)
-    acc = {n: ([], [], [], []) for n in ("dQ", "dK", "dV")}
-    for i, (q, k, v, ok) in enumerate(attn_case(L, hd, seed=1, kvh=kvh)):
-        O, lse = A.emulate_attn_fwd(q, k, v, ok, scale)
-        dO = rnd(L, hd, seed=5 + i, scale=0.5)
-        res = A.attn_bwd_bound(q, k, v, dO, O, lse, ok, scale)
-        for name, got in zip(("dQ", "dK", "dV"), A.emulate_attn_bwd(q, k, v, dO, O, lse, ok, scale)):
-            val, doc = res[name]
-            if rope and name != "dV":                  # the fused inverse RoPE: round to bf16, rotate in fp32, round at the store
-                a, b = got.float()[:, :64], got.float()[:, 64:]
-                got = torch.cat([a * cos + b * sin, b * cos - a * sin], 1).to(BF)
-                val, doc = A.rope_bwd_val(val, doc, cos.double(), sin.double())
-            for lst, x in zip(acc[name], (got, val.v, val.e, doc)):
-                lst.append(x)
-    for name, (got, v, e, doc) in acc.items():
-        assert passes(name, torch.cat(got), Val(torch.cat(v), torch.cat(e)), BF, doc=torch.cat(doc), cap_unit="ulp+doc")["ratio"] <= 1.0
+    for mask in attn_masks(L):
+        acc = {n: ([], [], [], []) for n in ("dQ", "dK", "dV")}
+        for i, (q, k, v, ok) in enumerate(attn_case(L, hd, seed=1, kvh=kvh, mask=mask)):
+            Lq = q.shape[0]
+            O, lse = A.emulate_attn_fwd(q, k, v, ok, scale)
+            dO = rnd(Lq, hd, seed=5 + i, scale=0.5)
+            res = A.attn_bwd_bound(q, k, v, dO, O, lse, ok, scale)
+            for name, got in zip(("dQ", "dK", "dV"), A.emulate_attn_bwd(q, k, v, dO, O, lse, ok, scale)):
+                val, doc = res[name]
+                if rope and name != "dV":                  # the fused inverse RoPE: round to bf16, rotate in fp32, round at the store
+                    n = got.shape[0]
+                    cos, sin = fr[:n].cos(), fr[:n].sin()
+                    a, b = got.float()[:, :64], got.float()[:, 64:]
+                    got = torch.cat([a * cos + b * sin, b * cos - a * sin], 1).to(BF)
+                    val, doc = A.rope_bwd_val(val, doc, cos.double(), sin.double())
+                for lst, x in zip(acc[name], (got, val.v, val.e, doc)):
+                    lst.append(x)
+        for name, (got, v, e, doc) in acc.items():
+            assert passes(f"{name} ({mask})", torch.cat(got), Val(torch.cat(v), torch.cat(e)), BF, doc=torch.cat(doc),
+                          cap_unit="ulp+doc")["ratio"] <= 1.0
+
+
+# ------------------------------------------------------------------------------------------------------ the GPU cases' layouts
+def _emulated_layout(layout, hd, G, seed):
+    """tests/test_accuracy_gpu.py's layout with the CPU emulation standing in for the kernels: (c, qkv parts, out, lse) as
+    rv_attn_fwd leaves them, the dead query rows of a Resampler layout included (zero q: a uniform softmax over all keys)"""
+    import test_accuracy_gpu as T
+    c = T.ATTN_LAYOUTS[layout]
+    L, H, scale = c["L"], 2, 1.0 / math.sqrt(hd)
+    qkv, q, k, v, starts, lens = T._attn_layout("cpu", L, hd, G, c.get("lens"), seed=seed, nq=c.get("nq"))
+    out, lse = torch.zeros(qkv.shape[0], H * hd, dtype=BF), torch.zeros(2, H, L)
+    masks = []
+    for s_ in range(2):
+        n, a = lens[s_], starts[s_]
+        masks.append(T._allowed(c, s_, n, "cpu"))                  # the kernel's view: all n queries of the row
+        for h in range(H):
+            o, l = A.emulate_attn_fwd(qkv[a:a + n, h * hd:(h + 1) * hd], k[s_, h // G, :n], v[s_, h // G, :n], masks[s_], scale)
+            out[a:a + n, h * hd:(h + 1) * hd], lse[s_, h, :n] = o, l
+    return T, c, (qkv, q, k, v, starts, lens), masks, out, lse
+
+
+def _full_cases():
+    import test_accuracy_gpu as T
+    return sorted({(kw["layout"], kw["hd"], kw["G"]) for _, kw in T.full_layout_cases(hd=[64, 128], G=[1, 2])})
+
+
+@pytest.mark.parametrize("layout,hd,G", _full_cases())
+def test_noncausal_gpu_layouts_pass_through_the_emulation(layout, hd, G):
+    """every non-causal layout of tests/test_accuracy_gpu.py at every head dim / kv_group it is admitted at, through the GPU cases' own
+    checkers with the CPU emulation in the kernels' place: inside the bound and under the discrimination cap (a layout over the cap
+    raises CapError here, before it costs a GPU run); the figures are printed.  Backward at head dim 128, as on the GPU."""
+    T, c, (qkv, q, k, v, starts, lens), masks, out, lse = _emulated_layout(layout, hd, G, seed=0)
+    what = f"emulated rv_attn_fwd (hd {hd}, kv_group {G}, {layout})"
+    for e in T._check_attn_fwd(c, "cpu", hd, G, out, lse, q, k, v, starts, lens, what):
+        assert e["ratio"] <= 1.0 and e["median_E_ulps"] <= A.CAP
+    if hd != 128:
+        return
+    T, c, (qkv, q, k, v, starts, lens), masks, out, lse = _emulated_layout(layout, hd, G, seed=1)
+    H, Hkv, scale = 2, 2 // G, 1.0 / math.sqrt(hd)
+    dO = T._attn_bwd_dO(c, "cpu", qkv.shape[0], starts, lens)
+    dqkv = torch.zeros_like(qkv)
+    for s_ in range(2):
+        n, a = lens[s_], starts[s_]
+        dk = torch.zeros(Hkv, n, hd)
+        dv = torch.zeros(Hkv, n, hd)
+        for h in range(H):
+            cols = slice(h * hd, (h + 1) * hd)
+            # the kernels accumulate the group's query heads in fp32 and round once: emulate_attn_bwd rounds per head, so its parts are
+            # recomputed here in fp32 from the same formula (dS and P rounded to bf16 for their MFMAs)
+            dq_, dk_, dv_ = _emulate_bwd_f32(qkv[a:a + n, cols], k[s_, h // G, :n], v[s_, h // G, :n], dO[a:a + n, cols], out[a:a + n, cols],
+                                             lse[s_, h, :n], masks[s_], scale)
+            dqkv[a:a + n, cols] = dq_.to(BF)
+            dk[h // G] += dk_
+            dv[h // G] += dv_
+        dqkv[a:a + n, H * hd:(H + Hkv) * hd] = dk.transpose(0, 1).reshape(n, Hkv * hd).to(BF)
+        dqkv[a:a + n, (H + Hkv) * hd:] = dv.transpose(0, 1).reshape(n, Hkv * hd).to(BF)
+    res = T._check_attn_bwd(c, "cpu", G, dqkv, dO, out, lse, q, k, v, starts, lens, f"emulated rv_attn_bwd (kv_group {G}, {layout})")
+    for e in res.values():
+        assert e["ratio"] <= 1.0 and e["median_E_ulps"] <= A.CAP
+
+
+def _emulate_bwd_f32(q, k, v, dO, O, lse, allowed, scale):
+    """accuracy.emulate_attn_bwd before its store: (dQ, dK, dV) in fp32"""
+    LOG2E = torch.tensor(1.4426950408889634, dtype=F32)
+    qf, kf, vf, dof = q.float(), k.float(), v.float(), dO.float()
+    c = torch.tensor(scale, dtype=F32) * LOG2E
+    S = torch.where(allowed, qf @ kf.t(), torch.tensor(-math.inf))
+    P = torch.exp2(S * c - (lse.float() * LOG2E)[:, None])
+    dS = P * (dof @ vf.t() - (dof * O.float()).sum(-1, keepdim=True))
+    sc = torch.tensor(scale, dtype=F32)
+    return (dS.to(BF).float() @ kf) * sc, (dS.to(BF).float().t() @ qf) * sc, P.to(BF).float().t() @ dof
 
 
 # ------------------------------------------------------------------------------------------------------ LM head

@@ -1044,7 +1044,10 @@ def c_lora_masks(lay, G, kind):
 # =========================================================================================== attention
 ATTN = {"causal-L200": dict(hd=128, causal=True, L=200), "causal-L1": dict(hd=128, causal=True, L=1),
         "full-hd64-L130": dict(hd=64, causal=False, L=130), "packed-L200": dict(hd=128, causal=True, L=200, seg=([40, 0], [120, 64])),
-        "pad-free-1-130": dict(hd=128, causal=True, L=130, rows=[1, 130])}
+        "pad-free-1-130": dict(hd=128, causal=True, L=130, rows=[1, 130]),
+        # causal = 0 at head dim 128, forward and backward (one pass per workgroup, an unpaired grid, every query block on the ragged
+        # last key tile); with pad-free rows of 1 and 130 tokens: the grid has two blocks per row, the one-token row uses one
+        "full-L130": dict(hd=128, causal=False, L=130), "full-pad-free-1-130": dict(hd=128, causal=False, L=130, rows=[1, 130])}
 GAP = 64          # sentinel columns between / behind the q, k, v ranges and behind out / dO's heads
 
 
@@ -1114,13 +1117,16 @@ def _attn_cases():
             for rope in (False, True):
                 for dkv in (0, 3):
                     out.append((f"{name}-G={G}-rope={rope}-dkv={dkv or 'default'}", dict(name=name, G=G, bwd=True, rope=rope, dkv=dkv)))
+    # head dim 128 has a second forward kernel (attn_fwd3_kernel, rv_set_attn_fwd_version(3)): the same cases on it
+    out += [(f"{cid}-fwd=3", dict(kw, fwdv=3)) for cid, kw in out if ATTN[kw["name"]]["hd"] == 128]
     return out
 
 
 @case(*_attn_cases())
-def c_attn(lay, name, G, bwd, rope, dkv):
+def c_attn(lay, name, G, bwd, rope, dkv, fwdv=0):
     """rv_attn_fwd, then rv_attn_bwd on its out / lse: everything outside the owned q | k | v columns and outside the sequences' token
-    rows is poison on the input side and guard on the output side; lse and the delta planes hold the sentinel at l >= row_len[s]"""
+    rows is poison on the input side and guard on the output side; lse and the delta planes hold the sentinel at l >= row_len[s].
+    fwdv: the forward kernel (rv_set_attn_fwd_version; 0 = the default)"""
     from rlaif_v_amd import hip, ops
     c = ATTN[name]
     g = _attn_geometry(c, G)
@@ -1135,8 +1141,12 @@ def c_attn(lay, name, G, bwd, rope, dkv):
         sh, e1 = lay.inp("seg_sh", i32(c["seg"][0])), lay.inp("seg_e1", i32(c["seg"][1]))
     if "rows" in c:
         roff, rlen = lay.inp("row_off", i32(g["starts"])), lay.inp("row_len", i32(g["lens"]))
-    call("rv_attn_fwd", qkv, ld(qkv), g["q0"], g["k0"], g["v0"], out, ld(out), lse, S, L, H, hd, int(c["causal"]), scale, sh, e1, G,
-         roff, rlen)
+    hip.lib().call("rv_set_attn_fwd_version", fwdv)
+    try:
+        call("rv_attn_fwd", qkv, ld(qkv), g["q0"], g["k0"], g["v0"], out, ld(out), lse, S, L, H, hd, int(c["causal"]), scale, sh, e1, G,
+             roff, rlen)
+    finally:
+        hip.lib().call("rv_set_attn_fwd_version", 0)
     if bwd:
         doh = rnd(ntok, H * hd + GAP, seed=L + 1)
         do = lay.inp("dO", doh, inner=g["ohole"])
