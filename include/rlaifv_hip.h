@@ -486,8 +486,9 @@ int rv_attn_decode(const void* q, long ldq, const void* kv, long ldkv, int k_col
  *   temperature == 0: greedy - the LOWEST index among equal maxima (rv_next_token_scores' argmax), u may be NULL, top_p is ignored
  *   and logp is the log-softmax of the penalised logits at that token.
  *   token int32 [M]; logp fp32 [M] = log-probability of the token under the final (kept, renormalised) distribution.
- *   The DISTRIBUTION is HF's; the map from random numbers to tokens is this kernel's own - torch.multinomial's stream cannot be
- *   reproduced.  One workgroup per row, fixed reduction order; logits are read only, inside [0, V_valid) of rows < M. */
+ *   The DISTRIBUTION is HF's for the processors named above - no top-k: the reference's sampling calls run behind transformers
+ *   4.35's default top_k = 50, which is rv_sample_token_topk below - and the map from random numbers to tokens is this kernel's
+ *   own - torch.multinomial's stream cannot be reproduced.  One workgroup per row, fixed reduction order; logits are read only, inside [0, V_valid) of rows < M. */
 int rv_sample_token(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids, float penalty,
                     float temperature, float top_p, const float* u, int* token, float* logp, void* stream);
 /* rv_sample_token_wide (csrc/sample_wide.hip; additive, ABI stays 7): rv_sample_token for 1 <= V_valid <= 262144 (Llama-3: 128256
@@ -510,6 +511,35 @@ long rv_sample_token_wide_workspace_floats(int M, int V_valid);
 int rv_sample_token_wide(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids, float penalty,
                          float temperature, float top_p, const float* u, int* token, float* logp, float* workspace,
                          long workspace_floats, void* stream);
+/* rv_sample_token_topk / rv_sample_token_wide_topk (additive, ABI stays 7): rv_sample_token / rv_sample_token_wide with HF's
+ *   TopKLogitsWarper in its place of the processor order (RepetitionPenalty, Temperature, TopK, TopP, softmax, multinomial) - the
+ *   same argument lists with `int top_k` behind top_p, and a new step between 2 and 3:
+ *   2b. let s_i be the fp32 score of step 2 and tau_k the largest value with #{i : s_i >= tau_k} >= top_k.  Tokens with
+ *      s_i < tau_k are dropped; EVERY token tied with tau_k stays, as in HF (the warper removes scores < the k-th largest), so more
+ *      than top_k tokens may survive; the comparison is by float value (-0.0 and +0.0 tie).  Z, step 3's threshold (1 - top_p) Z,
+ *      the kept mass, the draw and logp are then taken over the survivors, with the reductions of the base entry in the same
+ *      fixed order.  top_k == 0 or top_k >= V_valid: off.  top_k < 0 is refused.  Greedy (temperature == 0) ignores top_k as it
+ *      ignores top_p.
+ *   tau_k is selected on an order-preserving INTEGER key of s_i, never on exp(s_i - max): distinct scores can share a probability
+ *   (or 0), which would keep more than HF does.  rv_sample_token_topk: the row is in registers, the key is built bit by bit from
+ *   the top with 32 block-wide integer counts.  rv_sample_token_wide_topk: a radix select of 11 + 11 + 10 key bits, each a
+ *   2048-bin histogram in LDS filled with integer atomics (the first during the max pass, two more passes over the row); the
+ *   candidate list of step 3 then holds survivors only (at most top_k + ties; a wave's first 512 in LDS, further ones in its
+ *   part of the workspace).  No floating-point atomic anywhere.
+ *   With top-k off (0, >= V_valid, or greedy) both run the base entry's kernel: token and logp are the SAME BITS as
+ *   rv_sample_token / rv_sample_token_wide give.  The base entries' clauses hold unchanged: DETERMINISTIC (fixed reduction order;
+ *   the integer counts do not depend on the order of the atomics), a row's token and logp are a function of that row, u[m] and
+ *   its seen ids alone (not of M), CONTAINED (reads [0, V_valid) of rows < M only, for any ldl >= V_valid and any 4-byte-aligned
+ *   row start; writes token, logp and - the wide entry - the workspace only), and the wide entry's workspace is
+ *   rv_sample_token_wide_workspace_floats(M, V_valid) floats, uninitialised, holding nothing between calls.
+ *   The DISTRIBUTION is HF's for generate(do_sample=True, top_k=k, top_p=p, temperature=T, repetition_penalty=r); what the
+ *   reference's sampling calls leave unsaid comes from the checkpoint's generation_config.json and transformers 4.35's defaults
+ *   (top_k = 50): rlaif_v_amd/genconfig.py. */
+int rv_sample_token_topk(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids, float penalty,
+                         float temperature, float top_p, int top_k, const float* u, int* token, float* logp, void* stream);
+int rv_sample_token_wide_topk(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids,
+                              float penalty, float temperature, float top_p, int top_k, const float* u, int* token, float* logp,
+                              float* workspace, long workspace_floats, void* stream);
 
 /* ---- Beam-search decoding (csrc/beam.hip, rv_attn_decode_indexed in csrc/decode.hip; additive, ABI stays 7).  Replaces the decode
  *      steps of HF GenerationMixin._beam_search behind model.generate(do_sample=False, num_beams=3) in muffin/eval/muffin_vqa.py,

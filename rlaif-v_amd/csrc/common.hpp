@@ -56,6 +56,17 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return t;
 }
 
+// Order-preserving integer key of an fp32 score (the top-k select of the samplers): a < b as floats iff key(a) < key(b) as
+// unsigned, -0.0 and +0.0 share a key (x + 0 is +0 for both), -inf has the smallest key of all numbers (0x007fffff) and no
+// number has key 0.  score_of_key is the inverse.
+__device__ __forceinline__ uint32_t score_key(float x) {
+  const uint32_t b = __float_as_uint(x + 0.f);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float score_of_key(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
 // Bijective XCD-aware remap of a 1-D block id: block b runs on XCD b%8 (observed, speed only);
 // give every XCD a contiguous chunk of tile space so neighbouring tiles share an L2.
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

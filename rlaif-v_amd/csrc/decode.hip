@@ -385,13 +385,28 @@ __device__ __forceinline__ int block_min_i(int v, int* red) {
   return r;
 }
 
-template <int IPT>
+// the number of ids counted over the workgroup: wave butterfly, then the 16 wave counts
+__device__ __forceinline__ int block_count(int v, int* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int r = 0;
+  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += red[i];
+  return r;
+}
+
+// TOPK (rv_sample_token_topk with 0 < top_k < V while sampling) adds step 2b between the scores and the softmax; TOPK = false is
+// rv_sample_token's kernel as it was, top_k unread.
+template <int IPT, bool TOPK>
 __global__ __launch_bounds__(ST_THREADS) void sample_token_kernel(const float* __restrict__ logits, long ldl, int V,
                                                                   const int* __restrict__ seen_off,
                                                                   const int* __restrict__ seen_ids, float penalty,
                                                                   float temperature, float top_p,
                                                                   const float* __restrict__ u, int vec,
-                                                                  int* __restrict__ token, float* __restrict__ logp) {
+                                                                  int* __restrict__ token, float* __restrict__ logp,
+                                                                  int top_k) {
   extern __shared__ uint32_t st_bits[];            // [ceil(V / 32)] when the penalty is on
   __shared__ float red[16];
   __shared__ int redi[16];
@@ -449,6 +464,24 @@ __global__ __launch_bounds__(ST_THREADS) void sample_token_kernel(const float* _
   for (int w = 1; w < ST_THREADS / 64; ++w)
     if (red_mx[w] > mx || (red_mx[w] == mx && red_ix[w] < ix)) mx = red_mx[w], ix = red_ix[w];
   const float x_top = mx;
+  if constexpr (TOPK) {
+    // TopKLogitsWarper without the sort: tau = the largest score with at least top_k scores >= it, built bit by bit from the top
+    // on score_key (integer order = float order, so distinct scores never merge as their probabilities can); scores below tau
+    // leave, everything tied with it stays.  The keys take the scores' registers for the 32 counts; ids behind the row get
+    // key 0, below every score's.
+#pragma unroll
+    for (int e = 0; e < IPT; ++e) p[e] = __uint_as_float(base + e < V ? score_key(p[e]) : 0u);
+    uint32_t tk = 0u;
+    for (int bit = 31; bit >= 0; --bit) {
+      const uint32_t c = tk | (1u << bit);
+      int n = 0;
+#pragma unroll
+      for (int e = 0; e < IPT; ++e) n += __float_as_uint(p[e]) >= c ? 1 : 0;
+      if (block_count(n, redi) >= top_k) tk = c;
+    }
+#pragma unroll
+    for (int e = 0; e < IPT; ++e) p[e] = __float_as_uint(p[e]) < tk ? -INFINITY : score_of_key(__float_as_uint(p[e]));
+  }
   float loc = 0.f;
 #pragma unroll
   for (int e = 0; e < IPT; ++e) {
@@ -516,6 +549,23 @@ __global__ __launch_bounds__(ST_THREADS) void sample_token_kernel(const float* _
   }
 }
 
+// top_k off (0, >= V_valid) or greedy: rv_sample_token's kernel, whichever entry point asks
+static int sample_token_launch(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids,
+                               float penalty, float temperature, float top_p, int top_k, const float* u, int* token, float* logp,
+                               void* stream) {
+  const bool pen = seen_off != nullptr && penalty != 1.0f;
+  const int lds = pen ? (V_valid + 31) / 32 * 4 : 0;
+  const int vec = (((uintptr_t)logits & 15) == 0 && ldl % 4 == 0) ? 1 : 0;
+  const bool topk = top_k > 0 && top_k < V_valid && temperature != 0.f;
+#define ST_LAUNCH(IPT, TOPK)                                                                                                   \
+  launch<sample_token_kernel<IPT, TOPK>>(lds, dim3(M), dim3(ST_THREADS), stream, logits, ldl, V_valid, seen_off, seen_ids, penalty, \
+                                         temperature, top_p, u, vec, token, logp, top_k)
+  if (V_valid <= ST_THREADS * 8) return topk ? ST_LAUNCH(8, true) : ST_LAUNCH(8, false);
+  if (V_valid <= ST_THREADS * 32) return topk ? ST_LAUNCH(32, true) : ST_LAUNCH(32, false);
+  return topk ? ST_LAUNCH(64, true) : ST_LAUNCH(64, false);
+#undef ST_LAUNCH
+}
+
 extern "C" int rv_sample_token(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids,
                                float penalty, float temperature, float top_p, const float* u, int* token, float* logp,
                                void* stream) {
@@ -527,14 +577,20 @@ extern "C" int rv_sample_token(const float* logits, long ldl, int M, int V_valid
   RV_REQUIRE(penalty > 0.f, "rv_sample_token: the repetition penalty must be positive (1 = off)");
   RV_REQUIRE(temperature == 0.f || u != nullptr, "rv_sample_token: sampling needs the uniforms u[M]");
   RV_REQUIRE(seen_off == nullptr || seen_ids != nullptr, "rv_sample_token: seen_off without seen_ids");
-  const bool pen = seen_off != nullptr && penalty != 1.0f;
-  const int lds = pen ? (V_valid + 31) / 32 * 4 : 0;
-  const int vec = (((uintptr_t)logits & 15) == 0 && ldl % 4 == 0) ? 1 : 0;
-#define ST_LAUNCH(IPT)                                                                                                    \
-  launch<sample_token_kernel<IPT>>(lds, dim3(M), dim3(ST_THREADS), stream, logits, ldl, V_valid, seen_off, seen_ids, penalty, \
-                                   temperature, top_p, u, vec, token, logp)
-  if (V_valid <= ST_THREADS * 8) return ST_LAUNCH(8);
-  if (V_valid <= ST_THREADS * 32) return ST_LAUNCH(32);
-  return ST_LAUNCH(64);
-#undef ST_LAUNCH
+  return sample_token_launch(logits, ldl, M, V_valid, seen_off, seen_ids, penalty, temperature, top_p, 0, u, token, logp, stream);
+}
+
+extern "C" int rv_sample_token_topk(const float* logits, long ldl, int M, int V_valid, const int* seen_off, const int* seen_ids,
+                                    float penalty, float temperature, float top_p, int top_k, const float* u, int* token,
+                                    float* logp, void* stream) {
+  RV_REQUIRE(M > 0 && V_valid > 0 && ldl >= V_valid, "rv_sample_token_topk: M, V_valid > 0, ldl >= V_valid");
+  RV_REQUIRE(V_valid <= ST_THREADS * 64, "rv_sample_token_topk: V_valid <= 65536 (the row is held in registers)");
+  RV_REQUIRE(logits && token && logp, "rv_sample_token_topk: NULL buffer");
+  RV_REQUIRE(temperature >= 0.f, "rv_sample_token_topk: temperature must be >= 0 (0 = greedy)");
+  RV_REQUIRE(top_p > 0.f, "rv_sample_token_topk: top_p must be > 0 (>= 1 keeps every token)");
+  RV_REQUIRE(top_k >= 0, "rv_sample_token_topk: top_k must be >= 0 (0 or >= V_valid keeps every token)");
+  RV_REQUIRE(penalty > 0.f, "rv_sample_token_topk: the repetition penalty must be positive (1 = off)");
+  RV_REQUIRE(temperature == 0.f || u != nullptr, "rv_sample_token_topk: sampling needs the uniforms u[M]");
+  RV_REQUIRE(seen_off == nullptr || seen_ids != nullptr, "rv_sample_token_topk: seen_off without seen_ids");
+  return sample_token_launch(logits, ldl, M, V_valid, seen_off, seen_ids, penalty, temperature, top_p, top_k, u, token, logp, stream);
 }

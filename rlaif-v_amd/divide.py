@@ -16,8 +16,12 @@ defaults, i.e. add_special_tokens=True.  BOS: Llama-3's template already writes 
 tokenizer prepends the BOS id once more, so the ids start with TWO BOS tokens, exactly what the reference's models see.
 Answer text: ``tokenizer.decode(new_tokens, skip_special_tokens=True)``.
 
-Sampling: HF's distribution (temperature 0.2, then top_p 0.9) drawn from the uniforms of a seeded CPU generator - ``--seed`` fixes
-the output (the changeq stage uses seed + 1), but as in gen_data the stream is not torch.multinomial's.  A resumed run draws its
+Sampling: HF's processors (temperature 0.2, top_k when given, then top_p 0.9) drawn from the uniforms of a seeded CPU generator -
+``--seed`` fixes the output (the changeq stage uses seed + 1), but as in gen_data the stream is not torch.multinomial's.  The
+reference's pipeline call names temperature and top_p only, so under its transformers 4.35 top_k and the repetition penalty come
+from each checkpoint's generation_config.json, else from the library defaults (top_k = 50): ``--hf_defaults`` resolves them that
+way for each of the two checkpoints (genconfig.resolve_sampling) and is what reproduces the reference's DISTRIBUTION; without it
+there is no top-k, as before.  ``--top_k`` sets it by hand for both stages.  A resumed run draws its
 uniforms afresh for the items that are left, so it does not repeat the samples of an uninterrupted one.
 
 Files (the reference's names): with ``--path X.jsonl`` the divide stage writes
@@ -25,7 +29,7 @@ Files (the reference's names): with ``--path X.jsonl`` the divide stage writes
 ``....gq.jsonl`` (+ ``raw_changed_facts`` / ``changed_facts``) and ``construct_question_yesno`` ``....gq.qas.jsonl``.  An answer
 file that already exists is resumed: as many items as it has lines are skipped, new records are appended.
 
-    python -m rlaif_v_amd.divide --path answers.jsonl --divide_model DIR --changeq_model DIR --bs 8 --seed 0
+    python -m rlaif_v_amd.divide --path answers.jsonl --divide_model DIR --changeq_model DIR --bs 8 --seed 0 --hf_defaults
 """
 from __future__ import annotations
 
@@ -37,6 +41,8 @@ import os
 from typing import Callable, Dict, List, Optional, Sequence
 
 import torch
+
+from .genconfig import StoreGiven, cli_sampling, given_on_command_line
 
 TEMPERATURE, TOP_P, MAX_NEW_TOKENS = 0.2, 0.9, 256
 DIVIDE_WORDS = 300          # the divide prompt is cut to its first 300 space-separated pieces
@@ -156,9 +162,21 @@ def prompt_ids(tokenizer, messages: List[Dict]) -> torch.Tensor:
     return torch.as_tensor(list(tokenizer(text)["input_ids"]), dtype=torch.int64).reshape(-1)
 
 
+def stage_sampling(checkpoint_dir: Optional[str], top_k: Optional[int] = None, hf_defaults: bool = False) -> Dict:
+    """{temperature, top_p, top_k, repetition_penalty} of one stage: temperature 0.2 and top_p 0.9 are the explicit values of the
+    reference's call; ``top_k`` as given, else (``hf_defaults``) what that checkpoint's generation_config.json or transformers
+    4.35 says, else off; the repetition penalty likewise."""
+    given = {"temperature": TEMPERATURE, "top_p": TOP_P, "top_k": top_k, "repetition_penalty": None}
+    s = cli_sampling(checkpoint_dir, hf_defaults, given, {"temperature": TEMPERATURE, "top_p": TOP_P, "top_k": 0,
+                                                          "repetition_penalty": 1.0})
+    if s["top_k"] < 0:
+        raise ValueError("divide: top_k must be >= 0 (0 = off)")
+    return s
+
+
 def batch_inference(model, tokenizer, path: str, ans_file: str, key: str, wrap: Callable[[Dict], List[Dict]], batch_size: int = 8,
                     chunk_num: int = 1, chunk_idx: int = 0, max_tokens: int = MAX_NEW_TOKENS, start: int = 0, end: int = -1,
-                    seed: Optional[int] = 0) -> List[Dict]:
+                    seed: Optional[int] = 0, top_k: int = 0, repetition_penalty: float = 1.0) -> List[Dict]:
     """One stage over the selected items of ``path``: per item ``raw_{key}`` (the answer text) and ``{key}`` (get_facts of it)
     are added and the record is appended to ``ans_file`` at once.  Returns the records of the file, earlier ones included."""
     if getattr(model.cfg, "arch", "llava") != "text":
@@ -175,12 +193,17 @@ def batch_inference(model, tokenizer, path: str, ans_file: str, key: str, wrap: 
         os.makedirs(os.path.dirname(ans_file), exist_ok=True)
     gen = torch.Generator().manual_seed(int(seed)) if seed is not None else None
     stop = terminators(tokenizer)
+    extra = {}                                                    # the call of before when neither is asked for
+    if top_k:
+        extra["top_k"] = int(top_k)
+    if repetition_penalty != 1.0:
+        extra["repetition_penalty"] = float(repetition_penalty)
     with open(ans_file, "a" if done else "w") as out:
         for i0 in range(0, len(data), max(1, batch_size)):
             chunk = data[i0:i0 + max(1, batch_size)]
             prompts = [prompt_ids(tokenizer, wrap(it)) for it in chunk]
             toks = model.generate(prompts, None, max_new_tokens=max_tokens, temperature=TEMPERATURE, top_p=TOP_P,
-                                  eos_token_id=stop, generator=gen)
+                                  eos_token_id=stop, generator=gen, **extra)
             for it, new in zip(chunk, toks):
                 resp = tokenizer.decode(new[0], skip_special_tokens=True)
                 it[f"raw_{key}"] = resp
@@ -192,18 +215,23 @@ def batch_inference(model, tokenizer, path: str, ans_file: str, key: str, wrap: 
 
 
 def run(path: str, load: Callable[[str], tuple], divide_model: str, changeq_model: str, divide_suffix: str = "llama3-8b_divide",
-        chunk_num: int = 1, chunk_idx: int = 0, bs: int = 4, start: int = 0, end: int = -1, seed: Optional[int] = 0):
+        chunk_num: int = 1, chunk_idx: int = 0, bs: int = 4, start: int = 0, end: int = -1, seed: Optional[int] = 0,
+        top_k: Optional[int] = None, hf_defaults: bool = False):
     """The whole stage.  ``load(name) -> (model, tokenizer)``; the two checkpoints are loaded one after the other, the first is
-    released before the second is built.  Returns the three file names."""
+    released before the second is built.  ``top_k`` / ``hf_defaults``: stage_sampling, per checkpoint.  Returns the three file
+    names."""
     p_div, p_gq, p_qas = output_paths(path, start, end, chunk_num, chunk_idx, divide_suffix)
+    s_div, s_gq = stage_sampling(divide_model, top_k, hf_defaults), stage_sampling(changeq_model, top_k, hf_defaults)
     model, tokenizer = load(divide_model)
-    batch_inference(model, tokenizer, path, p_div, "facts", divide_messages, bs, chunk_num, chunk_idx, MAX_NEW_TOKENS, start, end, seed)
+    batch_inference(model, tokenizer, path, p_div, "facts", divide_messages, bs, chunk_num, chunk_idx, MAX_NEW_TOKENS, start, end, seed,
+                    top_k=s_div["top_k"], repetition_penalty=s_div["repetition_penalty"])
     del model, tokenizer
     if torch.cuda.is_available():
         torch.cuda.empty_cache()
     model, tokenizer = load(changeq_model)
     batch_inference(model, tokenizer, p_div, p_gq, "changed_facts", changeq_messages, bs, max_tokens=MAX_NEW_TOKENS,
-                    seed=None if seed is None else int(seed) + 1)
+                    seed=None if seed is None else int(seed) + 1, top_k=s_gq["top_k"],
+                    repetition_penalty=s_gq["repetition_penalty"])
     del model, tokenizer
     construct_question_yesno(p_gq, p_qas)
     return p_div, p_gq, p_qas
@@ -218,7 +246,7 @@ def load_text_model(ckpt_dir: str):
     return model, transformers.AutoTokenizer.from_pretrained(ckpt_dir, padding_side="left")
 
 
-def main(argv: Optional[Sequence[str]] = None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--path", type=str, required=True)
     ap.add_argument("--divide_model", type=str, required=True, help="HF LlamaForCausalLM directory of the claim splitter")
@@ -230,9 +258,19 @@ def main(argv: Optional[Sequence[str]] = None):
     ap.add_argument("--start", type=int, default=0)
     ap.add_argument("--end", type=int, default=-1)
     ap.add_argument("--seed", type=int, default=0)
-    args = ap.parse_args(argv)
+    ap.add_argument("--top_k", type=int, default=0, action=StoreGiven,
+                    help="0 = off; when not given, --hf_defaults takes each checkpoint's own")
+    ap.add_argument("--hf_defaults", action="store_true",
+                    help="take top_k and the repetition penalty, when not given here, from each checkpoint's "
+                         "generation_config.json, else from transformers 4.35's defaults (top_k 50)")
+    return ap
+
+
+def main(argv: Optional[Sequence[str]] = None):
+    args = build_parser().parse_args(argv)
     paths = run(args.path, load_text_model, args.divide_model, args.changeq_model, args.divide_suffix, args.chunk_num,
-                args.chunk_idx, args.bs, args.start, args.end, args.seed)
+                args.chunk_idx, args.bs, args.start, args.end, args.seed, top_k=given_on_command_line(args)["top_k"],
+                hf_defaults=args.hf_defaults)
     for p in paths:
         print(p)
     return paths

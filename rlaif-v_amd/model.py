@@ -1179,8 +1179,8 @@ class LlavaDPOModel:
 
     def generate(self, prompts, images, max_new_tokens: int, repeat: int = 1, temperature: float = 0.0, top_p: float = 1.0,
                  repetition_penalty: float = 1.0, eos_token_id=None,
-                 generator: Optional[torch.Generator] = None, return_scores: bool = False, num_beams: int = 1, *,
-                 _uniforms: Optional[torch.Tensor] = None, _forced_tokens: Optional[torch.Tensor] = None):
+                 generator: Optional[torch.Generator] = None, return_scores: bool = False, num_beams: int = 1,
+                 top_k: int = 0, *, _uniforms: Optional[torch.Tensor] = None, _forced_tokens: Optional[torch.Tensor] = None):
         """The sampling branch of the AI-feedback stage (muffin/llava15_gen_data.py:335-357: ``generate(do_sample=True,
         temperature=, max_new_tokens=, use_cache=True)`` on a dataset that repeats every item ``--repeat`` times): ``repeat``
         candidate answers per (image, prompt) with a KV cache.  ``prompts[k]``: 1-D input_ids with the image placeholder,
@@ -1191,11 +1191,15 @@ class LlavaDPOModel:
         host ``for`` over at most ``max_new_tokens`` steps and the finished flags are read back every 8 steps.  A finished
         sequence keeps its row and is decoded on until all are finished (its later tokens are dropped): with long answers of
         very different lengths that is work for nothing, the price of fixed chunks and no device-side waiting.
-        ``temperature`` 0 = greedy; else HF's processor order (repetition penalty, temperature, top_p) with uniforms drawn on
+        ``temperature`` 0 = greedy; else HF's processor order (repetition penalty, temperature, top_k, top_p) with uniforms drawn on
         the host from ``generator`` (a CPU torch.Generator; None = the default one): [max_new_tokens, n_seq] in one draw, so a
         seed fixes the output.  The distribution is HF's, the stream is not torch.multinomial's.  The repetition penalty
         covers the ids a sequence has GENERATED so far, no prompt id - the reference's generate starts from inputs_embeds, so
-        its processor sees no prompt id either (as forward_next_token_scores documents for the first token).  ``num_beams``
+        its processor sees no prompt id either (as forward_next_token_scores documents for the first token).  ``top_p`` < 1
+        keeps the smallest set of tokens whose mass reaches top_p; ``top_k`` > 0 first keeps the top_k highest scores and
+        everything tied with the last of them (HF's TopKLogitsWarper; rv_sample_token_topk / rv_sample_token_wide_topk), 0 =
+        off.  The reference's sampling calls name no top_k and so run with transformers 4.35's default of 50, or the value in the
+        checkpoint's generation_config.json: genconfig.resolve_sampling gives the values such a call runs with.  ``num_beams``
         exists to refuse beam search by name.  Test hooks, keyword-only: ``_uniforms`` (fp32 [max_new_tokens, n_seq]) plants
         the uniforms; ``_forced_tokens`` (int32 [n_seq, max_new_tokens]) feeds given tokens instead of the sampled ones
         (teacher forcing).
@@ -1211,6 +1215,8 @@ class LlavaDPOModel:
             raise NotImplementedError("generate(): OmniLMM (resampler splice) is not supported")
         if num_beams != 1:
             raise NotImplementedError("generate(): beam search (num_beams > 1) is not supported here - use beam_search()")
+        if int(top_k) != top_k or top_k < 0:
+            raise ValueError("generate(): top_k must be an integer >= 0 (0 = off)")
         if cfg.head_dim != 128:
             raise NotImplementedError("generate(): rv_attn_decode needs head_dim 128")
         text_only = getattr(cfg, "arch", "llava") == "text"
@@ -1273,7 +1279,7 @@ class LlavaDPOModel:
                                           (pre_off[c0:c1], pre_len[c0:c1], own_off[c0:c1], own_len[c0:c1]), caches, n_split,
                                           logits[c0:c1])
                 tok, _ = sampler(logits, M, cfg.vocab, uniforms[j] if sampling else None, float(temperature),
-                                 float(top_p), seen=seen, penalty=float(repetition_penalty), **extra)
+                                 float(top_p), seen=seen, penalty=float(repetition_penalty), top_k=int(top_k), **extra)
                 if forced_tokens is not None:
                     tok = forced_tokens[:, j]
                 tokens[:, j] = tok

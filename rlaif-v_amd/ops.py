@@ -825,10 +825,15 @@ def attn_decode(q: torch.Tensor, kv: torch.Tensor, H: int, hd: int, k_col0: int,
 
 
 def sample_token(logits: torch.Tensor, n_rows: int, v_valid: int, u: Optional[torch.Tensor], temperature: float = 0.0,
-                 top_p: float = 1.0, seen: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, penalty: float = 1.0):
+                 top_p: float = 1.0, seen: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, penalty: float = 1.0,
+                 top_k: int = 0):
     """One token per row of fp32 ``logits`` [rows, ld] over the columns [0, v_valid) (rv_sample_token): repetition penalty,
     temperature, top-p, softmax, inverse-CDF draw from the caller's uniforms ``u`` (fp32 [n_rows] in [0, 1)); temperature 0 =
-    greedy (u may be None).  Returns (token int32 [n_rows], logp fp32 [n_rows])."""
+    greedy (u may be None).  ``top_k`` > 0 (rv_sample_token_topk) keeps the top_k highest scores and everything tied with the
+    last of them, between temperature and top-p as HF's TopKLogitsWarper; 0 = off, the call of before.
+    Returns (token int32 [n_rows], logp fp32 [n_rows])."""
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError("sample_token: top_k must be an integer >= 0 (0 = off)")
     if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1 or not logits.is_cuda:
         raise ValueError("sample_token: logits must be a 2-D fp32 CUDA tensor with unit column stride")
     if not (0 < n_rows <= logits.shape[0] and 0 < v_valid <= logits.shape[1]):
@@ -857,6 +862,10 @@ def sample_token(logits: torch.Tensor, n_rows: int, v_valid: int, u: Optional[to
             seen_off = seen_ids = None
     token = torch.empty(n_rows, dtype=torch.int32, device=dev)
     logp = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    if top_k > 0:
+        hip.call("rv_sample_token_topk", logits, logits.stride(0), n_rows, v_valid, seen_off, seen_ids, float(penalty),
+                 float(temperature), float(top_p), int(top_k), u, token, logp)
+        return token, logp
     hip.call("rv_sample_token", logits, logits.stride(0), n_rows, v_valid, seen_off, seen_ids, float(penalty), float(temperature),
              float(top_p), u, token, logp)
     return token, logp
@@ -864,10 +873,12 @@ def sample_token(logits: torch.Tensor, n_rows: int, v_valid: int, u: Optional[to
 
 def sample_token_wide(logits: torch.Tensor, n_rows: int, v_valid: int, u: Optional[torch.Tensor], temperature: float = 0.0,
                       top_p: float = 1.0, seen: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, penalty: float = 1.0,
-                      workspace: Optional[torch.Tensor] = None):
+                      workspace: Optional[torch.Tensor] = None, top_k: int = 0):
     """``sample_token`` for vocabularies up to 262144 ids (rv_sample_token_wide): the same distribution, draw and return values
     with the row streamed instead of held in registers.  ``workspace``: fp32, at least ``sample_token_wide_workspace_floats``
-    elements (allocated here when None)."""
+    elements (allocated here when None).  ``top_k`` > 0: rv_sample_token_wide_topk, as ``sample_token``'s."""
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError("sample_token_wide: top_k must be an integer >= 0 (0 = off)")
     if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1 or not logits.is_cuda:
         raise ValueError("sample_token_wide: logits must be a 2-D fp32 CUDA tensor with unit column stride")
     if not (0 < n_rows <= logits.shape[0] and 0 < v_valid <= logits.shape[1]):
@@ -903,6 +914,10 @@ def sample_token_wide(logits: torch.Tensor, n_rows: int, v_valid: int, u: Option
         raise ValueError(f"sample_token_wide: workspace must be a contiguous fp32 tensor of >= {need} elements on the logits' device")
     token = torch.empty(n_rows, dtype=torch.int32, device=dev)
     logp = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    if top_k > 0:
+        hip.call("rv_sample_token_wide_topk", logits, logits.stride(0), n_rows, v_valid, seen_off, seen_ids, float(penalty),
+                 float(temperature), float(top_p), int(top_k), u, token, logp, workspace, workspace.numel())
+        return token, logp
     hip.call("rv_sample_token_wide", logits, logits.stride(0), n_rows, v_valid, seen_off, seen_ids, float(penalty),
              float(temperature), float(top_p), u, token, logp, workspace, workspace.numel())
     return token, logp

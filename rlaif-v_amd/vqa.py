@@ -10,6 +10,12 @@ the existing LlavaDPOModel.generate (greedy at temperature 0, else sampling).  B
 beam-sample mode; it is not implemented and refused by name.  The GPT-4 scoring half of the evaluation scripts is not part of
 this project.
 
+Sampling (``--num_beams 1 --temperature > 0``): ``--top_k`` is HF's TopKLogitsWarper (0 = off, the default).  ``--hf_defaults``
+takes every sampling parameter that is not on the command line from the checkpoint's generation_config.json, else from
+transformers 4.35's defaults (top_k = 50) - what a reference ``generate`` call that leaves them unsaid runs with
+(genconfig.resolve_sampling); without it nothing changes.  It concerns ``--num_beams 1`` alone: beam search samples nothing, so with
+``--num_beams > 1`` nothing is resolved.
+
 Question lines carry ``question`` and a base64 ``image`` or an ``image_path`` (autocheck.read_gen_dataset decodes them and
 applies the checkpoint's image_aspect_ratio).  Records: question_id (the running index), image_id (the line's ``image_id``, else
 its ``image_url``), prompt (the question as given), text (the decoded new tokens, special tokens skipped, stripped), model_id.
@@ -28,6 +34,9 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from .autocheck import read_gen_dataset, wrap_question_for_llava15
+from .genconfig import StoreGiven, cli_sampling, given_on_command_line
+
+DEFAULTS = {"temperature": 0.2, "top_p": 1.0, "top_k": 0, "repetition_penalty": 1.0}     # without --hf_defaults
 
 MODEL_ID = "llava-v1.5-7b"          # muffin_vqa.py:35 writes this name whatever the checkpoint
 
@@ -40,7 +49,8 @@ def get_chunk(lst: Sequence, n: int, k: int):
 
 def answer_questions(model, tokenizer, lines: Sequence[Dict], num_beams: int = 3, temperature: float = 0.0,
                      top_p: Optional[float] = None, max_new_tokens: int = 1024, prompts_per_call: int = 4, seed: Optional[int] = 0,
-                     model_id: str = MODEL_ID, length_penalty: float = 1.0) -> List[Dict]:
+                     model_id: str = MODEL_ID, length_penalty: float = 1.0, top_k: int = 0,
+                     repetition_penalty: float = 1.0) -> List[Dict]:
     """``lines``: dicts with ``question``, ``image`` (what ``encode_images`` takes for ONE image) and ``image_id`` or
     ``image_url`` (read_gen_dataset keeps ``image_url`` under ``metainfos``).  ``prompts_per_call`` questions share one call;
     an answer does not depend on the questions next to it."""
@@ -67,8 +77,13 @@ def answer_questions(model, tokenizer, lines: Sequence[Dict], num_beams: int = 3
             answers, _ = model.beam_search(prompts, images, max_new_tokens=max_new_tokens, num_beams=num_beams, eos_token_id=eos,
                                            length_penalty=length_penalty)
         else:
+            extra = {}                                        # the call of before when neither is asked for
+            if top_k:
+                extra["top_k"] = int(top_k)
+            if repetition_penalty != 1.0:
+                extra["repetition_penalty"] = float(repetition_penalty)
             out = model.generate(prompts, images, max_new_tokens=max_new_tokens, repeat=1, temperature=temperature,
-                                 top_p=1.0 if top_p is None else top_p, eos_token_id=eos, generator=gen)
+                                 top_p=1.0 if top_p is None else top_p, eos_token_id=eos, generator=gen, **extra)
             answers = [o[0] for o in out]
         for n, it in enumerate(chunk):
             image_id = it["image_id"] if "image_id" in it else it.get("image_url", it.get("metainfos", {}).get("image_url"))
@@ -87,8 +102,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--conv-mode", type=str, default="llava_v1")
     ap.add_argument("--num-chunks", type=int, default=1)
     ap.add_argument("--chunk-idx", type=int, default=0)
-    ap.add_argument("--temperature", type=float, default=0.2)
-    ap.add_argument("--top_p", type=float, default=None)
+    ap.add_argument("--temperature", type=float, default=0.2, action=StoreGiven)
+    ap.add_argument("--top_p", type=float, default=None, action=StoreGiven)
+    ap.add_argument("--top_k", type=int, default=0, action=StoreGiven, help="0 = off; sampling only")
+    ap.add_argument("--hf_defaults", action="store_true",
+                    help="sampling (--num_beams 1) only: take every sampling parameter not given here from the checkpoint's "
+                         "generation_config.json, else from transformers 4.35's defaults (top_k 50); with --num_beams > 1 "
+                         "nothing is sampled and nothing is resolved")
     ap.add_argument("--num_beams", type=int, default=3)
     ap.add_argument("--max_new_tokens", type=int, default=1024, help="the reference hard-codes 1024")
     ap.add_argument("--batch_size", type=int, default=4, help="questions per call")
@@ -96,8 +116,20 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def sampling_args(args) -> Dict:
+    """{temperature, top_p, top_k, repetition_penalty} of the parsed command line"""
+    # beam search samples nothing: --hf_defaults then must not turn the default temperature into the file's (beam-sample mode)
+    s = cli_sampling(os.path.expanduser(args.model_path), args.hf_defaults and args.num_beams == 1, given_on_command_line(args),
+                     DEFAULTS)
+    if s["top_k"] < 0:
+        raise ValueError("--top_k must be >= 0 (0 = off)")
+    return s
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    sampling = sampling_args(args)
+    args.temperature = sampling["temperature"]
     if args.conv_mode != "llava_v1":
         raise NotImplementedError(f"--conv-mode {args.conv_mode}: only llava_v1 (conv_llava_v1) prompts are built")
     if args.num_beams > 1 and args.temperature > 0:
@@ -112,8 +144,9 @@ def main(argv=None):
         aspect = json.load(f).get("image_aspect_ratio")
     lines = get_chunk(read_gen_dataset(os.path.expanduser(args.question_file), image_aspect_ratio=aspect), args.num_chunks,
                       args.chunk_idx)
-    records = answer_questions(model, tokenizer, lines, num_beams=args.num_beams, temperature=args.temperature, top_p=args.top_p,
-                               max_new_tokens=args.max_new_tokens, prompts_per_call=args.batch_size, seed=args.seed)
+    records = answer_questions(model, tokenizer, lines, num_beams=args.num_beams, temperature=args.temperature,
+                               top_p=sampling["top_p"], max_new_tokens=args.max_new_tokens, prompts_per_call=args.batch_size,
+                               seed=args.seed, top_k=sampling["top_k"], repetition_penalty=sampling["repetition_penalty"])
     answers_file = os.path.expanduser(args.answers_file)
     os.makedirs(os.path.dirname(os.path.abspath(answers_file)), exist_ok=True)
     with open(answers_file, "w") as f:

@@ -11,7 +11,9 @@ not end with status 0 (nothing more is started on a device after a fault, an abo
             those rows (rv_gemm_nt_skinny_bf16, N = 128256, K = 4096, fp32 out), interleaved, median of ``--reps`` timings of 20
             back-to-back launches each.  Rows: the LM head's own output of random weights scaled to a spread of several units
             (at temperature 0.2 a peaked distribution: the candidate lists stay in LDS), greedy on the same rows, and the worst
-            case - temperature 1, top-p 0.9 on a flat row, every token a candidate, every wave spills to the workspace.
+            case - temperature 1, top-p 0.9 on a flat row, every token a candidate, every wave spills to the workspace.  Next to
+            the stage's row and the flat row the same call with top_k = 50 (rv_sample_token_wide_topk: two more passes over
+            the row for the radix select, then at most 50 + ties candidates).
   generate  ms per decode step (HIP events around every _decode_step) and tokens/s per batch, the sampler and the LM head per
             step (HIP events around ops.sample_token_wide; the LM head from a skinny GEMM of the batch's rows timed alone), and the
             weight-streaming floor: decoder + LM-head bytes every step must read, divided by the HBM streaming rate.  That rate
@@ -33,7 +35,7 @@ HBM_STREAM_TBS = 6.29
 V, D = 128256, 4096
 BATCHES = (4, 8)
 PROMPT_TOKENS, NEW_TOKENS = 300, 256
-TEMPERATURE, TOP_P = 0.2, 0.9
+TEMPERATURE, TOP_P, TOP_K = 0.2, 0.9, 50
 
 
 def _merge(path, key, value):
@@ -84,9 +86,12 @@ def part_sampler(args):
         spread = float(logits.max() - logits.min())
         fns = {"lm_head_skinny_gemm": lambda: ops.gemm_nt_skinny(h, w, out=logits, out_f32=True),
                "wide_T0.2_p0.9_lm_head_rows": lambda: ops.sample_token_wide(logits, M, V, u, TEMPERATURE, TOP_P, workspace=ws),
+               "wide_T0.2_p0.9_k50_lm_head_rows": lambda: ops.sample_token_wide(logits, M, V, u, TEMPERATURE, TOP_P, workspace=ws,
+                                                                                  top_k=TOP_K),
                "wide_greedy_lm_head_rows": lambda: ops.sample_token_wide(logits, M, V, None, 0.0, 1.0, workspace=ws),
                "wide_T1_p1_lm_head_rows": lambda: ops.sample_token_wide(logits, M, V, u, 1.0, 1.0, workspace=ws),
-               "wide_T1_p0.9_flat_rows_spill": lambda: ops.sample_token_wide(flat, M, V, u, 1.0, TOP_P, workspace=ws)}
+               "wide_T1_p0.9_flat_rows_spill": lambda: ops.sample_token_wide(flat, M, V, u, 1.0, TOP_P, workspace=ws),
+               "wide_T1_p0.9_k50_flat_rows": lambda: ops.sample_token_wide(flat, M, V, u, 1.0, TOP_P, workspace=ws, top_k=TOP_K)}
         us = _time(fns, args.reps)
         rows.append(dict(M=M, V=V, K=D, logit_spread=round(spread, 2), us=us,
                          lm_head_tbs=round(V * D * 2 / us["lm_head_skinny_gemm"] / 1e6, 3)))

@@ -16,6 +16,10 @@ not end with status 0 (nothing more is started on a device after a fault, an abo
             weight-streaming floor: decoder + LM-head bytes every step must read, divided by the HBM streaming rate.  That rate
             (6.29 TB/s, a float4 copy) is the measuring guide's figure, not a measurement of this machine: the output says so.
 
+  sampler   one rv_sample_token call at M = 60 rows of V = 32000 (6 prompts x 10 samples) on the LM head's own output of random
+            weights, next to the LM-head skinny GEMM that writes those rows: temperature 0.7 (the stage's) and 0.2 with top-p 0.9,
+            each without top-k and with top_k = 50 (rv_sample_token_topk: 32 block-wide counts for the select), the calls
+            interleaved, median of ``--reps`` timings of 20 back-to-back launches each.
   launches  launches per decode step and chunk: the library's (through hip.call) and every device kernel (torch.profiler),
             from 2- and 3-layer models of the 7B widths.
 
@@ -90,6 +94,43 @@ def part_gemm(args):
             print(f"[bench_generate] {name} M={M}: nt {old_us:.1f} us, skinny {new_us:.1f} us ({N * K * 2 / new_us / 1e6:.2f} TB/s)", flush=True)
     _merge(args.out, "skinny_gemm", dict(device=torch.cuda.get_device_name(0), reps=args.reps, rows=rows))
     print(json.dumps(dict(part="gemm", rows=len(rows))))
+
+
+def part_sampler(args):
+    import torch
+    from rlaif_v_amd import ops
+    dev = torch.device("cuda", 0)
+    M, V, D = 60, 32000, 4096
+    g = torch.Generator().manual_seed(0)
+    w = (torch.randn(V, D, generator=g) * 0.02).bfloat16().to(dev)
+    h = (torch.randn(M, D, generator=g) * 1.5).bfloat16().to(dev)
+    logits = torch.empty(M, V, dtype=torch.float32, device=dev)
+    ops.gemm_nt_skinny(h, w, out=logits, out_f32=True)
+    u = torch.rand(M, generator=g).to(dev)
+    fns = {"lm_head_skinny_gemm": lambda: ops.gemm_nt_skinny(h, w, out=logits, out_f32=True)}
+    for T, p in ((0.7, 1.0), (0.7, 0.9), (0.2, 0.9)):
+        for k in (0, 50):
+            fns[f"T{T}_p{p}_k{k}"] = lambda T=T, p=p, k=k: ops.sample_token(logits, M, V, u, T, p, top_k=k)
+    fns["greedy"] = lambda: ops.sample_token(logits, M, V, None, 0.0, 1.0)
+    t = {k: [] for k in fns}
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(args.reps):
+        for key, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(20):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            t[key].append(e0.elapsed_time(e1) / 20 * 1e3)
+    us = {k: round(statistics.median(v), 2) for k, v in t.items()}
+    print(f"[bench_generate] sampler M={M} V={V}: {us}", flush=True)
+    _merge(args.out, "sampler", dict(device=torch.cuda.get_device_name(0), reps=args.reps, M=M, V=V, K=D,
+                                     logit_spread=round(float(logits.max() - logits.min()), 2), us=us,
+                                     note="microseconds per call, HIP events around 20 back-to-back launches, median of reps"))
+    print(json.dumps(dict(part="sampler", us=us)))
 
 
 def part_launches(args):
@@ -224,11 +265,12 @@ def part_generate(args):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--part", choices=("gemm", "generate", "launches"), help="run one part in this process (what the driver starts)")
+    ap.add_argument("--part", choices=("gemm", "generate", "launches", "sampler"), help="run one part in this process (what the driver starts)")
     ap.add_argument("--layers", type=int, default=32, help="debug only: anything but 32 is not the 7B configuration")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--limits", type=int, nargs=3, default=[240, 600, 240], help="time limits of the three parts, seconds")
+    ap.add_argument("--limits", type=int, nargs=3, default=[240, 600, 240], help="time limits of the gemm, generate and launches parts, seconds")
+    ap.add_argument("--sampler-limit", type=int, default=120, help="time limit of the sampler part, seconds")
     ap.add_argument("--out", default=os.path.join(os.environ.get("RV_RECORD_DIR") or os.path.join(REPO, "bench_outputs"), "r11_generate.json"))
     args = ap.parse_args()
     if args.part == "gemm":
@@ -237,7 +279,9 @@ def main():
         return part_generate(args)
     if args.part == "launches":
         return part_launches(args)
-    for part, limit in zip(("gemm", "generate", "launches"), args.limits):
+    if args.part == "sampler":
+        return part_sampler(args)
+    for part, limit in zip(("gemm", "generate", "launches", "sampler"), list(args.limits) + [args.sampler_limit]):
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--part", part, "--layers", str(args.layers),
                "--warmup", str(args.warmup), "--reps", str(args.reps), "--out", args.out]
         rc = subprocess.run(cmd).returncode
