@@ -590,6 +590,52 @@ int rv_beam_step(const float* cand_val, const int* cand_parent, const int* cand_
                  float* run_score, int* parent, int* token, const int* hist_a, int* hist_b, const int* rows_a, int* rows_b, long ld_t,
                  int* hyp_tokens, int* hyp_len, float* hyp_score, int* n_hyp, int* done, void* stream);
 
+/* ---- Continuous batching of candidate generation (csrc/decode_state.hip; additive, ABI stays 7).  Replaces nothing in the
+ *      reference, whose generate() decodes a fixed batch until its longest answer ends; it replaces the per-step torch
+ *      bookkeeping of LlavaDPOModel.generate (tokens[:, j] = tok, seen_ids[:, j] = tok, done |= ..., rows.step(j)), which
+ *      assumes every row is at step j, by scatters that let every row - "slot" - be at a step of its own, so that a finished
+ *      slot can be given to the next waiting prompt (LlavaDPOModel.generate_continuous, rlaif_v_amd/schedule.py).
+ *
+ * Per-slot state, int32 [S] each: len (tokens recorded so far), budget (1 <= budget <= T: the most tokens the slot's sequence
+ *   may have), done (0 = live; a slot that was never admitted must hold done != 0), pre_off / pre_len (the cache rows of its
+ *   prompt), own_off (first cache row of the slot's own region of >= T rows; constant).  Tables, row s = slot s, row length
+ *   ld_t >= T: out_tokens int32 (the generated ids), seen_ids int32 (the same ids for the sampler's repetition penalty, -1 = none:
+ *   pass it to rv_sample_token as seen_ids with seen_off[s] = s * ld_t), u_table fp32 (the uniform of each step, read only).
+ *   eos_ids: a HOST array of n_eos ids, 0 <= n_eos <= 8 (NULL when 0); it travels by value with the launch.
+ *
+ * rv_decode_advance: once per step, after the sampler; one thread per slot, any S >= 1.  token int32 [S] = the sampled tokens.
+ *   A live slot s (done == 0; a live slot with len outside [0, budget) is marked done and records nothing): writes token[s] to
+ *   out_tokens[s][len] and seen_ids[s][len], increments len, and sets done when the token is one of eos_ids or len == budget.
+ *   Then, for every slot, what the next decode step and sampler call take:
+ *     still live:  tok_in = token[s], pos = pre_len + len - 1 (RoPE position), dst = own_off + len - 1 (the cache row of the token's
+ *                  K | V), spans (pre_off, pre_len_eff = pre_len, own_off, own_len = len) for rv_attn_decode, u_next = u_table[s][len];
+ *     PARKED (done, now or before; never admitted): tok_in = 0, pos = 0, dst = own_off, pre_len_eff = 0, own_len = 1, u_next = 0.5 -
+ *                  the step writes and then attends row 0 of the slot's own region: finite, satisfies rv_attn_decode's
+ *                  pre_len + own_len >= 1, touches no other slot's rows, and the token sampled for it is recorded nowhere.
+ * rv_decode_admit: gives the n listed slots (1 <= n <= 64 per call, each slot at most once) to new sequences.  slots,
+ *   new_pre_off, new_pre_len, new_budget: HOST int32 [n] (checked here, then passed by value); token int32 [n] on the device = the
+ *   first token of each, sampled from its prompt's prefill logits.  One workgroup per listed slot: sets the slot's row of
+ *   seen_ids to -1 ([0, T)), len = 0, done = 0, pre_off, pre_len, budget, then performs rv_decode_advance's step for the first
+ *   token.  Slots not listed are not touched.
+ *
+ *   CONTAINED: for slot s the kernels write column len[s] (its value on entry) of row s of out_tokens / seen_ids - rv_decode_admit
+ *   also columns [0, T) of row s of seen_ids - and entry s of the [S] state and output arrays; nothing else.  Every table index
+ *   is derived from values clamped in the kernel (budget to [0, T], len to [0, budget)), and an emitted dst is never outside
+ *   [own_off[s], own_off[s] + budget[s]), for parked slots too.  u_table is read at [s][len] with 1 <= len < T only.
+ *   REFUSED before any launch (rc 1 and an rv_last_error text that starts with the entry point's name): S < 1, T < 1, ld_t < T,
+ *   S * ld_t beyond int32, n_eos outside [0, 8], a NULL or misaligned table / state / output array, and for rv_decode_admit
+ *   n outside [1, 64], a NULL list, a slot index outside [0, S), a slot listed twice, a budget outside [1, T], a negative span.
+ *   No waiting on the device, no communication between workgroups, plain vector stores only; the result does not depend on the
+ *   order in which slots are processed. */
+int rv_decode_advance(const int* token, int* len, const int* budget, int* done, const int* pre_off, const int* pre_len,
+                      const int* own_off, const int* eos_ids, int n_eos, int* out_tokens, int* seen_ids, const float* u_table,
+                      long ld_t, int S, int T, int* tok_in, int* pos, int* dst, int* pre_len_eff, int* own_len, float* u_next,
+                      void* stream);
+int rv_decode_admit(const int* slots, const int* new_pre_off, const int* new_pre_len, const int* new_budget, int n,
+                    const int* token, int* len, int* budget, int* done, int* pre_off, int* pre_len, const int* own_off,
+                    const int* eos_ids, int n_eos, int* out_tokens, int* seen_ids, const float* u_table, long ld_t, int S, int T,
+                    int* tok_in, int* pos, int* dst, int* pre_len_eff, int* own_len, float* u_next, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,8 @@ metainfos carries one), raw_question, answer (the decoded new tokens, special to
 Command line (the jsonl format of the reference's GenDataset in; one record per line out):
     python -m rlaif_v_amd.gen_data --checkpoint CKPT --ds_name questions.jsonl --answer_file out.jsonl \\
         --repeat 10 --temperature 0.7 --max_tokens 512 --seed 0 --hf_defaults
+``--continuous --slots 64`` runs the same stage with continuous batching (generate_continuous): the same records in the same
+order, other samples (the uniforms are then a hash of the seed and the item's index), fewer decode steps.
 """
 from __future__ import annotations
 
@@ -39,13 +41,21 @@ DEFAULTS = {"temperature": 0.7, "top_p": 1.0, "top_k": 0, "repetition_penalty": 
 
 def generate_answers(model, tokenizer, items: Sequence[Dict], repeat: int = 1, temperature: float = 0.7, top_p: float = 1.0,
                      max_tokens: int = 10, seed: Optional[int] = 0, prompts_per_call: int = 6, model_path: Optional[str] = None,
-                     repetition_penalty: float = 1.0, top_k: int = 0) -> List[Dict]:
+                     repetition_penalty: float = 1.0, top_k: int = 0, continuous: bool = False, slots: int = 64,
+                     index_base: int = 0) -> List[Dict]:
     """``items``: dicts with ``question`` (text), ``image`` (what ``encode_images`` takes for ONE image: a preprocessed
     [3, H, W] tensor or a raw uint8 [H, W, 3] image), optionally ``question_id`` (default: the item's index) and ``metainfos``.
     ``repeat`` samples per item at ``temperature`` (0 = greedy: the copies are then equal); ``seed``: the CPU generator the
-    uniforms come from (None: torch's default generator).  ``prompts_per_call`` items share one ``generate`` call."""
+    uniforms come from (None: torch's default generator).  ``prompts_per_call`` items share one ``generate`` call.
+    ``continuous``: the items go through ``generate_continuous`` with ``slots`` decode rows instead (a finished row is given to
+    the next item; ``prompts_per_call`` then plays no part), item n under the request index ``index_base`` + n - its absolute
+    index in the question file when ``index_base`` is the shard's --start - so that its samples depend on ``seed`` and that
+    index alone, not on the shard or the other items.  The records are the same, in item order."""
     if getattr(model.cfg, "arch", "llava") == "omnilmm":
         raise NotImplementedError("gen_data: OmniLMM generation is not implemented (LlavaDPOModel.generate is LLaVA-1.5 only)")
+    if continuous:
+        return _generate_answers_continuous(model, tokenizer, items, repeat, temperature, top_p, max_tokens, seed, model_path,
+                                            repetition_penalty, top_k, slots, index_base)
     gen = torch.Generator().manual_seed(int(seed)) if seed is not None else None
     eos = getattr(tokenizer, "eos_token_id", None)
     mm = getattr(model.cfg, "mm_use_im_start_end", False)
@@ -73,6 +83,38 @@ def generate_answers(model, tokenizer, items: Sequence[Dict], repeat: int = 1, t
     return records
 
 
+def _record(it: Dict, default_id, answer: str, model_path: Optional[str]) -> Dict:
+    meta = it.get("metainfos", {})
+    rec = {"question_id": it.get("question_id", default_id)}
+    if "ds_question_id" in meta:
+        rec["ds_question_id"] = meta["ds_question_id"]
+    rec.update(raw_question=it["question"], answer=answer, metainfos=meta, model_path=model_path)
+    return rec
+
+
+def _generate_answers_continuous(model, tokenizer, items, repeat, temperature, top_p, max_tokens, seed, model_path,
+                                 repetition_penalty, top_k, slots, index_base) -> List[Dict]:
+    from .splice import IMAGE_TOKEN_INDEX
+    eos = getattr(tokenizer, "eos_token_id", None)
+    mm = getattr(model.cfg, "mm_use_im_start_end", False)
+    prompts = [torch.as_tensor(wrap_question_for_llava15(it["question"], tokenizer, mm)) for it in items]
+    if not prompts:
+        return []
+    n_img = int(model.cfg.n_image_tokens)
+    longest = max(int(p.numel()) + (n_img - 1) * int((p == IMAGE_TOKEN_INDEX).sum()) for p in prompts)     # spliced lengths
+    out = dict(model.generate_continuous(((p, it["image"]) for p, it in zip(prompts, items)), max_new_tokens=max_tokens,
+                                         slots=max(int(slots), int(repeat)), repeat=repeat, temperature=temperature, top_p=top_p,
+                                         top_k=int(top_k), repetition_penalty=repetition_penalty, eos_token_id=eos,
+                                         seed=0 if seed is None else int(seed), max_prompt_tokens=longest,
+                                         request_indices=range(index_base, index_base + len(items))))
+    records: List[Dict] = []
+    for n, it in enumerate(items):
+        for r in range(repeat):
+            answer = tokenizer.decode(out[index_base + n][r], skip_special_tokens=True).strip()
+            records.append(_record(it, n, answer, model_path))
+    return records
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--checkpoint", type=str, required=True)
@@ -89,6 +131,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--num_beam", type=int, default=-1)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch_size", type=int, default=6, help="items per generate call (x --repeat decode rows)")
+    ap.add_argument("--continuous", action="store_true",
+                    help="continuous batching: --slots decode rows, a finished row is given to the next item "
+                         "(LlavaDPOModel.generate_continuous); an item's samples then depend on --seed and its index in the "
+                         "question file alone")
+    ap.add_argument("--slots", type=int, default=64, help="decode rows of --continuous")
     ap.add_argument("--start", "--start_pos", dest="start", type=int, default=0)
     ap.add_argument("--end", "--end_pos", dest="end", type=int, default=-1)
     return ap
@@ -117,7 +164,8 @@ def main(argv=None):
     records = generate_answers(model, tokenizer, items, repeat=args.repeat, temperature=sampling["temperature"],
                                top_p=sampling["top_p"], max_tokens=args.max_tokens, seed=args.seed,
                                prompts_per_call=args.batch_size, model_path=args.checkpoint,
-                               repetition_penalty=sampling["repetition_penalty"], top_k=sampling["top_k"])
+                               repetition_penalty=sampling["repetition_penalty"], top_k=sampling["top_k"],
+                               **(dict(continuous=True, slots=args.slots, index_base=max(args.start, 0)) if args.continuous else {}))
     with open(args.answer_file, "w") as f:
         for rec in records:
             f.write(json.dumps(rec) + "\n")

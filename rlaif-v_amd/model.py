@@ -946,12 +946,14 @@ class LlavaDPOModel:
                     xn=xn if keep else None, xn2=xn2 if keep else None, act=act if keep else None)
         return x_next, branch, lctx
 
-    def _run_stack(self, x: torch.Tensor, plan, save: bool = False, caches: Optional[List[torch.Tensor]] = None):
+    def _run_stack(self, x: torch.Tensor, plan, save: bool = False, caches: Optional[List[torch.Tensor]] = None,
+                   cache_rows: Optional[torch.Tensor] = None):
         """The decoder stack over the spliced bf16 embeddings ``x`` [n_tokens, hidden] under the pass state of _begin_pass: every
         surface's driver.  Returns (the final residual stream, the layers' backward contexts - empty unless ``save``).
         ``save`` under --gradient_checkpointing keeps only each layer's INPUT (fp32 stream: with its pending branch added) and
         backward runs the layer again.  ``caches``: per layer a [rows, 2 kv_dim] bf16 buffer whose first n_tokens rows receive the
-        layer's roped K | V columns."""
+        layer's roped K | V columns; with ``cache_rows`` (int32 [n_tokens], generate_continuous) token t goes to row cache_rows[t]
+        instead."""
         cfg = self.cfg
         if self.resid_fp32:
             x = ops.cast_bf16_to_f32(x)          # embedding / feature rows are bf16 values: exact
@@ -960,8 +962,10 @@ class LlavaDPOModel:
         pending, layers_ctx = None, []
         for i in range(cfg.layers):
             x_next, branch, lctx = self._layer_fwd(i, x, pending, plan, cos, sin, keep or caches is not None)
-            if caches is not None:
+            if caches is not None and cache_rows is None:
                 caches[i][:plan.n_tokens].copy_(lctx["qkv"][:, cfg.hidden:])      # device copy of the roped K | V columns (plumbing)
+            elif caches is not None:
+                ops.scatter_rows(lctx["qkv"][:, cfg.hidden:], cache_rows, caches[i])
             if keep:
                 layers_ctx.append(lctx)
             elif save:
@@ -972,14 +976,15 @@ class LlavaDPOModel:
             x = ops.add_f32_bf16(x, pending)     # the last layer's branch joins the fp32 stream
         return x, layers_ctx
 
-    def _last_position_logits(self, plan: SplicePlan, images, caches: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
+    def _last_position_logits(self, plan: SplicePlan, images, caches: Optional[List[torch.Tensor]] = None,
+                              cache_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Forward-only read-out behind every row's last token: embed + splice, the stack, the final norm at ``plan.last_idx`` and
         the LM head in fp32.  Returns [round_up(n_seq, 64), vocab_padded] logits (rows >= n_seq are the LM head of zero rows)."""
         cfg, st = self.cfg, self.store
         self._begin_pass()
         feats = self.encode_images(images)
         x = ops.splice_fwd(plan.src, st.p("model.embed_tokens.weight"), feats, cfg.hidden)
-        x, _ = self._run_stack(x, plan, caches=caches)
+        x, _ = self._run_stack(x, plan, caches=caches, cache_rows=cache_rows)
         n = plan.n_seq
         hsel = torch.zeros(max(64, ops.round_up(n, 64)), cfg.hidden, dtype=BF16, device=self.device)
         ops.rmsnorm_fwd(x, st.p("model.norm.weight"), cfg.rms_eps, row_idx=plan.last_idx, out=hsel[:n], want_rstd=False)
@@ -1126,13 +1131,14 @@ class LlavaDPOModel:
             return ops.next_token_scores(logits, n_q, cfg.vocab, want, seen=seen, penalty=float(repetition_penalty))
 
     # ------------------------------------------------------------------ KV-cached candidate generation
-    def _prefill(self, prompts, images, caches: Optional[List[torch.Tensor]] = None):
+    def _prefill(self, prompts, images, caches: Optional[List[torch.Tensor]] = None, cache_rows: Optional[torch.Tensor] = None):
         """One plain causal pad-free row per prompt through the training forward's stack (_last_position_logits: its bits).  Returns fp32 last-position logits [round_up(n, 64), vocab_padded] (rows >= n are the LM head of zero rows).
-        ``caches``: per layer a [rows, 2 kv_dim] bf16 buffer; the layer's roped K | V rows are copied to its first n_tokens rows."""
+        ``caches``: per layer a [rows, 2 kv_dim] bf16 buffer; the layer's roped K | V rows are copied to its first n_tokens rows,
+        or with ``cache_rows`` (int32 [n_tokens] on the device) scattered to the rows it names."""
         cfg = self.cfg
         plan = build_branch_plan([[p] for p in prompts], cfg.n_image_tokens, cfg.model_max_length, splicer=self._row_splicer(),
                                  pad_free=True, packed=False).to(self.device)
-        return self._last_position_logits(plan, images, caches)
+        return self._last_position_logits(plan, images, caches, cache_rows)
 
     def _decode_step(self, tok: torch.Tensor, pos: torch.Tensor, dst: torch.Tensor, spans, caches: List[torch.Tensor],
                      n_split: int, out: torch.Tensor, own_rows: Optional[torch.Tensor] = None, cur_own_len: int = 0):
@@ -1299,6 +1305,193 @@ class LlavaDPOModel:
                 for r in range(repeat):
                     out[-1].append(cut_behind_eos(host[k * repeat + r], eos_ids))
             return (out, torch.stack(scores)) if return_scores else out
+
+    # ------------------------------------------------------------------ continuous batching of candidate generation
+    def generate_continuous(self, requests, max_new_tokens: int, slots: int = 64, repeat: int = 1, temperature: float = 0.0,
+                            top_p: float = 1.0, top_k: int = 0, repetition_penalty: float = 1.0, eos_token_id=None, seed: int = 0,
+                            max_prompt_tokens: Optional[int] = None, poll_every: int = 8, num_beams: int = 1,
+                            request_indices=None, prefill_prompts: int = 8, regions: Optional[int] = None, *,
+                            _uniforms=None, _scores=None, _scheduler: Optional[list] = None):
+        """``generate()``'s sampling with the finished rows refilled: a GENERATOR over ``requests``, any iterable of
+        ``(prompt_ids, image[, max_new_tokens_i])`` consumed lazily (a DataLoader can feed it), that yields
+        ``(request_index, [tokens of sample 0 .. repeat - 1])`` in completion order.  ``request_indices``: an iterable of ints
+        consumed in step with ``requests`` (default 0, 1, ...) - the index a request is reported and seeded under.
+        The decode step has ``slots`` rows, each at a step of its own (ops.DecodeState, rv_decode_advance): _decode_step per
+        chunk of <= 64 slots, the sampler over all slots, rv_decode_advance; a finished or unused slot is parked on the first
+        row of its own cache region.  The done flags are read back when schedule.SlotScheduler says so (every ``poll_every``
+        steps, sooner when every live budget ends sooner); a request is admitted whole - ``repeat`` free slots and one of
+        ``regions`` (default min(slots, 3 * (slots // repeat))) prompt regions of ``max_prompt_tokens`` rows (default model_max_length; a
+        region is what the cache reserves per live prompt, so pass the longest spliced prompt when it is known) - at most
+        ``prefill_prompts`` per _prefill call, whose K | V rows are scattered to their regions (schedule.SlotRows) and whose
+        last-position logits give each sample's first token (rv_decode_admit).
+        BITS: every kernel of a sequence's path is ``generate()``'s and none of them lets a row see its neighbours, and
+        n_split = min(8, max(1, (max_prompt_tokens + max_new_tokens) // 256)) is a function of the engine's capacity only: a
+        sequence's tokens do not depend on ``slots``, on who shares the step with it or on the order of arrival, and equal
+        ``generate([prompt], [image], budget, repeat)`` with the same uniforms whenever that call's n_split is the same.
+        UNIFORMS: step t of sample r of request i draws schedule.uniform_table(seed, i, max_new_tokens, repeat)[t, r], a hash
+        of (seed, i, r, t) alone - no generator is consumed in call order, so a shard that starts at another item draws the
+        same numbers for it.  ``max_new_tokens_i`` (<= max_new_tokens) is a request's own budget: one int, or ``repeat`` ints, one per
+        sample.
+        Test hooks, keyword-only: ``_uniforms`` (callable index -> fp32 [max_new_tokens, repeat]) replaces the table;
+        ``_scores`` (callable (index, sample, step, fp32 logits [vocab])) sees every row a live slot is sampled from (rows
+        behind a sequence's end included, until the poll that frees the slot); ``_scheduler`` (a list) receives the
+        SlotScheduler.  Refused by name before anything is launched: OmniLMM, un-merged LoRA, head_dim != 128,
+        num_beams != 1, repeat > slots; a prompt longer than ``max_prompt_tokens`` when its request is reached."""
+        cfg = self.cfg
+        if self.lora is not None:
+            raise NotImplementedError("generate_continuous(): un-merged LoRA adapters are not supported - merge_lora() first")
+        if getattr(cfg, "arch", "llava") == "omnilmm" or self._row_splicer() is not None:
+            raise NotImplementedError("generate_continuous(): OmniLMM (resampler splice) is not supported")
+        if num_beams != 1:
+            raise NotImplementedError("generate_continuous(): beam search (num_beams > 1) is not supported - use beam_search()")
+        if cfg.head_dim != 128:
+            raise NotImplementedError("generate_continuous(): rv_attn_decode needs head_dim 128")
+        if int(top_k) != top_k or top_k < 0:
+            raise ValueError("generate_continuous(): top_k must be an integer >= 0 (0 = off)")
+        if max_new_tokens < 1 or repeat < 1 or slots < 1 or poll_every < 1 or prefill_prompts < 1:
+            raise ValueError("generate_continuous(): max_new_tokens, repeat, slots, poll_every and prefill_prompts must be >= 1")
+        if repeat > slots:
+            raise ValueError(f"generate_continuous(): repeat {repeat} > slots {slots} (a request is admitted whole)")
+        max_prompt = int(cfg.model_max_length if max_prompt_tokens is None else max_prompt_tokens)
+        if max_prompt < 1:
+            raise ValueError("generate_continuous(): max_prompt_tokens must be >= 1")
+        eos_ids = eos_id_set(eos_token_id)
+        if eos_ids is not None and len(eos_ids) > 8:
+            raise ValueError("generate_continuous(): at most 8 EOS ids (rv_decode_advance)")
+        ops.sampler_for(cfg.vocab)
+        return self._continuous(requests, int(max_new_tokens), int(slots), int(repeat), float(temperature), float(top_p), int(top_k),
+                                float(repetition_penalty), eos_ids, int(seed), max_prompt, int(poll_every), request_indices,
+                                int(prefill_prompts), regions, _uniforms, _scores, _scheduler)
+
+    def _continuous(self, requests, T, S, repeat, temperature, top_p, top_k, penalty, eos_ids, seed, max_prompt, poll_every,
+                    request_indices, prefill_prompts, regions, uniforms_of, scores_hook, sched_out):
+        """The loop of generate_continuous (a generator: the checks above run at the call, this at the first ``next``)."""
+        from .schedule import SlotRows, SlotScheduler, uniform_table
+        cfg, dev = self.cfg, self.device
+        text_only = getattr(cfg, "arch", "llava") == "text"
+        sampler, wide = ops.sampler_for(cfg.vocab)
+        sched = SlotScheduler(S, repeat, regions, poll_every)
+        if sched_out is not None:
+            sched_out.append(sched)
+        rows = SlotRows(sched.regions, max_prompt, S, T)
+        sampling = temperature != 0.0
+        feed = iter(requests)
+        index_feed = iter(request_indices) if request_indices is not None else None
+        with self._eval_mode():
+            self._rope(max_prompt + T)
+            n_split = min(8, max(1, (max_prompt + T) // 256))        # the engine's capacity only: the same bits whoever shares the step
+            caches = [torch.empty(rows.n_rows, 2 * cfg.kv_dim, dtype=BF16, device=dev) for _ in range(cfg.layers)]
+            state = ops.DecodeState(S, T, rows.own_off, dev, eos_ids)
+            seen = state.seen if penalty != 1.0 else None
+            extra = {}
+            if wide:
+                extra["workspace"] = torch.empty(ops.sample_token_wide_workspace_floats(S, cfg.vocab), dtype=torch.float32, device=dev)
+            logits = torch.zeros(S, cfg.vocab_padded, dtype=torch.float32, device=dev)
+            chunks = rows.chunks
+            age = [0] * S                  # sampler rounds a slot's sequence has had (host count, for the scores hook)
+            results: Dict[int, list] = {}
+            position, exhausted = 0, False
+            while True:
+                # ---- admission: whole requests, at most prefill_prompts per prefill
+                while not exhausted and sched.room() > 0:
+                    batch, cap = [], min(sched.room(), prefill_prompts)
+                    while len(batch) < cap:
+                        try:
+                            req = next(feed)
+                        except StopIteration:
+                            exhausted = True
+                            break
+                        index = position if index_feed is None else int(next(index_feed))
+                        position += 1
+                        prompt, image = req[0], req[1]
+                        budget = req[2] if len(req) > 2 and req[2] is not None else T
+                        budget = [int(b) for b in budget] if isinstance(budget, (list, tuple)) else [int(budget)] * repeat
+                        if len(budget) != repeat or not all(1 <= b <= T for b in budget):
+                            raise ValueError(f"generate_continuous(): request {index}: max_new_tokens {budget} outside [1, {T}] "
+                                             f"(one value, or one per sample)")
+                        if text_only:
+                            if image is not None:
+                                raise ValueError(f"generate_continuous(): request {index}: a text-only model (TextLMConfig) takes image=None")
+                            if bool((torch.as_tensor(prompt) == IMAGE_TOKEN_INDEX).any()):
+                                raise ValueError(f"generate_continuous(): request {index}: a prompt of a text-only model holds the image placeholder")
+                        elif image is None:
+                            raise ValueError(f"generate_continuous(): request {index}: image=None needs a text-only model (TextLMConfig)")
+                        if index in results or any(index == b[0] for b in batch):
+                            raise ValueError(f"generate_continuous(): request index {index} is used twice")
+                        batch.append((index, prompt, image, budget))
+                    if not batch:
+                        break
+                    prompts = [b[1] for b in batch]
+                    cpu_plan = build_branch_plan([[p] for p in prompts], cfg.n_image_tokens, cfg.model_max_length, splicer=None,
+                                                 pad_free=True, packed=False)
+                    lens = cpu_plan.row_len.tolist()
+                    for (index, _, _, _), n in zip(batch, lens):
+                        if n > max_prompt:
+                            raise ValueError(f"generate_continuous(): request {index}: a spliced prompt of {n} tokens is longer than "
+                                             f"max_prompt_tokens = {max_prompt}")
+                    images = None
+                    if not text_only:
+                        images = [b[2] for b in batch]
+                        if all(torch.is_tensor(im) for im in images) and len({(im.shape, im.dtype) for im in images}) == 1 \
+                                and images[0].dtype != torch.uint8:
+                            images = torch.stack(images)
+                    ad_slots, ad_off, ad_len, ad_budget, prompt_of, regs = [], [], [], [], [], []
+                    for k, (index, _, _, budget) in enumerate(batch):
+                        region, ss = sched.admit(index, budget)
+                        regs.append(region)
+                        if sampling:
+                            table = uniforms_of(index) if uniforms_of is not None else uniform_table(seed, index, T, repeat)
+                            table = torch.as_tensor(table, dtype=torch.float32)
+                            if tuple(table.shape) != (T, repeat):
+                                raise ValueError(f"generate_continuous(): the uniforms of a request must be [{T}, {repeat}]")
+                            state.u_table[torch.tensor(ss, device=dev)] = table.t().contiguous().to(dev)
+                        results[index] = [None] * repeat
+                        for r, s in enumerate(ss):
+                            ad_slots.append(s), ad_off.append(rows.region_off(region)), ad_len.append(lens[k])
+                            ad_budget.append(budget[r]), prompt_of.append(k)
+                    first = self._prefill(prompts, images, caches, rows.prefill_rows(regs, lens).to(dev))
+                    first = first[torch.tensor(prompt_of, device=dev)]                  # [admitted slots, vocab_padded]
+                    slot_t = torch.tensor(ad_slots, device=dev)
+                    n_new = len(ad_slots)
+                    x = {"workspace": torch.empty(ops.sample_token_wide_workspace_floats(n_new, cfg.vocab), dtype=torch.float32,
+                                                  device=dev)} if wide else {}
+                    tok, _ = sampler(first, n_new, cfg.vocab, state.u_table[slot_t, 0].contiguous() if sampling else None, temperature,
+                                     top_p, seen=None, penalty=1.0, top_k=top_k, **x)        # nothing generated yet: nothing to penalise
+                    if scores_hook is not None:
+                        for n, s in enumerate(ad_slots):
+                            scores_hook(*sched.owner[s], 0, first[n, :cfg.vocab].clone())
+                    for s in ad_slots:
+                        age[s] = 1
+                    ops.decode_admit(state, ad_slots, ad_off, ad_len, ad_budget, tok)
+                if not sched.live:
+                    if exhausted:
+                        return
+                    continue
+                # ---- decode steps until the next look at the flags
+                for _ in range(sched.steps_to_poll()):
+                    for c0, c1 in chunks:
+                        if sched.chunk_live(c0, c1):
+                            self._decode_step(state.tok_in[c0:c1], state.pos[c0:c1], state.dst[c0:c1],
+                                              (state.pre_off[c0:c1], state.pre_len_eff[c0:c1], state.own_off[c0:c1],
+                                               state.own_len[c0:c1]), caches, n_split, logits[c0:c1])
+                    tok, _ = sampler(logits, S, cfg.vocab, state.u_next if sampling else None, temperature, top_p, seen=seen,
+                                     penalty=penalty, top_k=top_k, **extra)
+                    if scores_hook is not None:
+                        for s, o in enumerate(sched.owner):
+                            if o is not None:
+                                scores_hook(*o, age[s], logits[s, :cfg.vocab].clone())
+                                age[s] += 1
+                    ops.decode_advance(state, tok)
+                    sched.step()
+                # ---- the read-back: lengths and flags, then the rows of the slots that have finished
+                lens_h, done_h = state.flags()
+                finished, complete = sched.poll(done_h)
+                if finished:
+                    got = state.out_tokens[torch.tensor([s for s, _, _ in finished], device=dev)].cpu().tolist()
+                    for (s, index, sample), row in zip(finished, got):
+                        results[index][sample] = cut_behind_eos(row[:lens_h[s]], eos_ids)
+                for index in complete:
+                    yield index, results.pop(index)
 
     # ------------------------------------------------------------------ beam-search decoding (the evaluation stage)
     def beam_search(self, prompts, images, max_new_tokens: int, num_beams: int = 3, eos_token_id: Optional[int] = None,

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -1053,6 +1053,75 @@ def beam_step(state: BeamState, cand, j: int, eos_token_id: Optional[int] = None
              state.hyp_score, state.n_hyp, state.done)
     state.hist, state.hist_next = state.hist_next, state.hist
     state.own_rows, state.own_rows_next = state.own_rows_next, state.own_rows
+    return state
+
+
+# ------------------------------------------------------------------------------------- continuous batching (csrc/decode_state.hip)
+class DecodeState:
+    """The device state of ``S`` decode slots of at most ``T`` tokens each (rv_decode_advance / rv_decode_admit): per slot its
+    length, budget, done flag and prompt span, the token / seen-id / uniform tables, and what the next decode step and sampler
+    call read (``tok_in``, ``pos``, ``dst``, the spans, ``u_next``).  ``own_off`` int32 [S]: first cache row of each slot's own
+    region.  Every slot starts parked (done = 1).  The int32 arrays are rows of ONE [11, S] tensor, so ``flags()`` is a single
+    read-back."""
+    _ROWS = ("len", "budget", "done", "pre_off", "pre_len", "own_off", "tok_in", "pos", "dst", "pre_len_eff", "own_len")
+
+    def __init__(self, n_slots: int, max_tokens: int, own_off: torch.Tensor, device, eos_ids=None):
+        S, T = int(n_slots), int(max_tokens)
+        if S < 1 or T < 1:
+            raise ValueError("DecodeState: n_slots and max_tokens must be >= 1")
+        if own_off.numel() != S:
+            raise ValueError(f"DecodeState: own_off needs {S} entries")
+        eos = [] if eos_ids is None else [int(e) for e in eos_ids]
+        if len(eos) > 8:
+            raise ValueError("DecodeState: at most 8 EOS ids (rv_decode_advance)")
+        self.S, self.T, self.device = S, T, torch.device(device)
+        self.eos = torch.tensor(eos, dtype=torch.int32) if eos else None          # host: it travels by value with each launch
+        self.ints = torch.zeros(len(self._ROWS), S, dtype=torch.int32, device=device)
+        for k, name in enumerate(self._ROWS):
+            setattr(self, name, self.ints[k])
+        self.done.fill_(1)
+        self.own_len.fill_(1)
+        self.own_off.copy_(own_off.to(torch.int32))
+        self.dst.copy_(self.own_off)
+        self.out_tokens = torch.zeros(S, T, dtype=torch.int32, device=device)
+        self.seen_ids = torch.full((S, T), -1, dtype=torch.int32, device=device)
+        self.u_table = torch.full((S, T), 0.5, dtype=torch.float32, device=device)
+        self.u_next = torch.full((S,), 0.5, dtype=torch.float32, device=device)
+        self.seen = (torch.arange(S + 1, dtype=torch.int32, device=device) * T, self.seen_ids.view(-1))   # the sampler's view
+
+    def _tail(self):
+        return (self.len, self.budget, self.done, self.pre_off, self.pre_len, self.own_off, self.eos,
+                0 if self.eos is None else self.eos.numel(), self.out_tokens, self.seen_ids, self.u_table, self.T, self.S, self.T,
+                self.tok_in, self.pos, self.dst, self.pre_len_eff, self.own_len, self.u_next)
+
+    def flags(self) -> Tuple[List[int], List[int]]:
+        """(len, done) of every slot on the host: one read-back."""
+        host = self.ints[:3].cpu()
+        return host[0].tolist(), host[2].tolist()
+
+
+def decode_advance(state: DecodeState, token: torch.Tensor) -> DecodeState:
+    """Records the sampled ``token`` int32 [S] of every live slot and prepares the next step (rv_decode_advance)."""
+    if token.dtype != torch.int32 or token.numel() != state.S or not token.is_contiguous() or token.device != state.device:
+        raise ValueError(f"decode_advance: token must be contiguous int32 [{state.S}] on {state.device}")
+    hip.call("rv_decode_advance", token, *state._tail())
+    return state
+
+
+def decode_admit(state: DecodeState, slots, pre_off, pre_len, budget, token: torch.Tensor) -> DecodeState:
+    """Hands the listed ``slots`` to new sequences with the prompt spans (``pre_off``, ``pre_len``) and ``budget`` (host int
+    sequences of one length n) and advances them by their first ``token`` int32 [n] on the device (rv_decode_admit, at most
+    64 slots per launch)."""
+    host = [torch.as_tensor(list(v), dtype=torch.int32).contiguous() for v in (slots, pre_off, pre_len, budget)]
+    n = host[0].numel()
+    if n < 1 or any(h.numel() != n for h in host):
+        raise ValueError("decode_admit: slots, pre_off, pre_len and budget are lists of one length >= 1")
+    if token.dtype != torch.int32 or token.numel() != n or not token.is_contiguous() or token.device != state.device:
+        raise ValueError(f"decode_admit: token must be contiguous int32 [{n}] on {state.device}")
+    with torch.cuda.device(state.device):          # the first arguments are host lists: name the launch's device here
+        for c in range(0, n, 64):
+            part = [h[c:c + 64].contiguous() for h in host]
+            hip.lib().call("rv_decode_admit", *part, part[0].numel(), token[c:c + 64], *state._tail(), hip.stream_ptr(state.device))
     return state
 
 
