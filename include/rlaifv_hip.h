@@ -569,6 +569,27 @@ int rv_attn_decode_indexed(const void* q, long ldq, const void* kv, long ldkv, i
 long rv_beam_topk_workspace_floats(int G, int K);
 int rv_beam_topk(const float* logits, long ldl, const float* score, int G, int K, int V_valid, float* cand_val, int* cand_parent,
                  int* cand_tok, float* lse, float* workspace, long workspace_floats, void* stream);
+/* rv_beam_topk_penalty: rv_beam_topk with HF's RepetitionPenaltyLogitsProcessor where beam search runs its logits processors:
+ *   between the log-softmax and the score add (omnilmm/omnilmm_gen_data.py:306-314: num_beams with repetition_penalty=1.1).
+ *   Per row m = g K + b:  lp[v] = (x[v] - max) - log Z  in fp32 exactly as rv_beam_topk; every DISTINCT id v among
+ *   hist[m * ld_h + 0 .. n_hist) (int32) with 0 <= v < V_valid is penalised ONCE:  lp[v] = lp[v] < 0 ? lp[v] * penalty :
+ *   lp[v] / penalty  (HF gathers and scatters: a duplicate id is not penalised twice); ids outside [0, V_valid), -1 included, are
+ *   ignored; then value = lp[v] + score[m] - one multiply, one add, one rounding each, never fused.  (lp <= +0 always - the row's
+ *   maximum gives x - max = 0 and Z >= 1 - so the division is met by lp = +0 alone, where quotient and product are the same +0:
+ *   the kernel multiplies.)  Then rv_beam_topk's selection and merge: the same order of equal values, V_valid <= 65536,
+ *   1 <= K <= 8, the dead-beam score -1e9, the same workspace (rv_beam_topk_workspace_floats(G, K)), the same determinism.
+ *   READ: logits columns [0, V_valid) of rows [0, G K); score [G K]; hist entries [0, n_hist) of rows [0, G K) at row stride ld_h
+ *   - entries at column >= n_hist are never read, and hist is not read at all when penalty == 1 or n_hist == 0.
+ *   WRITTEN: cand_val / cand_parent / cand_tok [G][2K], lse [G K] - the UN-penalised max + log Z - and the workspace.
+ *   hist is the token-history table rv_beam_step writes: at step j row m holds the j tokens of running beam m, so a beam search
+ *   passes n_hist = j, ld_h = the table's row length.  The ids of a row become a bit set of ceil(V_valid / 32) words in LDS
+ *   (8 KB at 65536 ids), read when the register row is transformed.  With penalty == 1, n_hist == 0 or hist == NULL the plain
+ *   kernel is launched: rv_beam_topk's bits on every output.
+ *   rc 1: everything rv_beam_topk refuses; penalty <= 0; n_hist < 0 or n_hist > ld_h; hist == NULL with n_hist > 0 and
+ *   penalty != 1; hist not 4-byte aligned; G K ld_h beyond int32. */
+int rv_beam_topk_penalty(const float* logits, long ldl, const float* score, int G, int K, int V_valid, const int* hist, long ld_h,
+                         int n_hist, float penalty, float* cand_val, int* cand_parent, int* cand_tok, float* lse, float* workspace,
+                         long workspace_floats, void* stream);
 /* rv_beam_step: step j (0-based, of at most T) of GenerationMixin._beam_search (transformers 5.x, do_sample=False,
  *   early_stopping=False, one EOS id, generation from inputs_embeds: the prompt length counts 0) on the 2K candidates of every
  *   group, one wave per group.  A candidate "stops" when its token is eos_token_id (-1: none) or when `last` = (j == T - 1).

@@ -29,17 +29,40 @@ __device__ __forceinline__ bool bt_after(float v, int i, float wv, int wi) { ret
 // winner is found by a wave butterfly and a pass over the 16 wave results in wave order, and only the thread that owned the
 // winner looks through its registers again.  "Not yet chosen" is "strictly behind the last winner in the order", so no
 // element is marked and a value may be anything finite.
-template <int IPT>
+// PEN (rv_beam_topk_penalty with a history and penalty != 1) puts HF's RepetitionPenaltyLogitsProcessor between the log-softmax
+// and the score add: the row's history ids become an LDS bit set of ceil(V / 32) words, as in sample_token_kernel (a set: a
+// duplicate id counts once), and a thread reads the one or two words that cover its ids - p[] is never indexed with an id.
+// PEN = false is rv_beam_topk's kernel as it was, `pen` unread.
+struct BeamPenalty {
+  const int* hist;
+  long ld_h;
+  int n_hist;
+  float penalty;
+};
+
+template <int IPT, bool PEN>
 __global__ __launch_bounds__(BT_THREADS) void beam_topk_row_kernel(const float* __restrict__ logits, long ldl, int V,
                                                                    const float* __restrict__ score, int vec, int n,
                                                                    float* __restrict__ row_val, int* __restrict__ row_tok,
-                                                                   float* __restrict__ lse) {
+                                                                   float* __restrict__ lse, const BeamPenalty pen) {
+  extern __shared__ uint32_t bt_bits[];            // [ceil(V / 32)] when PEN
   __shared__ float red[16];
   __shared__ float red_v[16];
   __shared__ int red_i[16];
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* row = logits + (long)m * ldl;
   const int base = tid * IPT;
+  if constexpr (PEN) {
+    const int nw = (V + 31) >> 5;
+    for (int i = tid; i < nw; i += BT_THREADS) bt_bits[i] = 0u;
+    __syncthreads();
+    const int* h = pen.hist + (long)m * pen.ld_h;
+    for (int i = tid; i < pen.n_hist; i += BT_THREADS) {
+      const int id = h[i];
+      if (id >= 0 && id < V) atomicOr(&bt_bits[id >> 5], 1u << (id & 31));
+    }
+    __syncthreads();                                   // also stands before the first read of bt_bits below
+  }
   float p[IPT];
   if (vec && base + IPT <= V) {
 #pragma unroll
@@ -64,8 +87,28 @@ __global__ __launch_bounds__(BT_THREADS) void beam_topk_row_kernel(const float* 
   for (int e = 0; e < IPT; ++e) loc += base + e < V ? expf(p[e] - mx) : 0.f;
   const float logz = logf(block_sum(loc, red));
   const float sc = score[m];
+  if constexpr (PEN) {
+    // HF's rule is l < 0 ? l * penalty : l / penalty.  A log-probability is never positive here: the row's maximum gives
+    // x - mx = +0 and contributes expf(0) = 1 to Z, so log Z >= +0 and l <= +0; the division is met by l = +0 alone, where it
+    // gives the product's +0 (a NaN stays a NaN either way).  So the product IS the rule, and the division's temporaries do not
+    // push the 64-ids-per-thread instantiation (128 VGPRs at 1024 threads) into scratch.
+    // ids [base + c, base + c + BT_CHUNK) lie in one word of the set (base is a multiple of IPT, BT_CHUNK divides 32); a word is
+    // read only where its first id is valid, and an id >= V of a valid word has no bit (the fill checks id < V)
+    constexpr int BT_CHUNK = IPT < 32 ? IPT : 32;
 #pragma unroll
-  for (int e = 0; e < IPT; ++e) p[e] = ((p[e] - mx) - logz) + sc;        // log_softmax in fp32, then ONE add (HF's order)
+    for (int c = 0; c < IPT; c += BT_CHUNK) {
+      const uint32_t w = base + c < V ? bt_bits[(base + c) >> 5] >> ((base + c) & 31) : 0u;
+#pragma unroll
+      for (int e = c; e < c + BT_CHUNK; ++e) {
+        float l = (p[e] - mx) - logz;                  // log_softmax in fp32 ...
+        if ((w >> (e - c)) & 1u) l = __fmul_rn(l, pen.penalty);     // ... HF's processor on it, never fused with the add ...
+        p[e] = l + sc;                                 // ... then ONE add (HF's order)
+      }
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < IPT; ++e) p[e] = ((p[e] - mx) - logz) + sc;      // log_softmax in fp32, then ONE add (HF's order)
+  }
   if (tid == 0) lse[m] = mx + logz;
   float bv = 0.f, wv = 0.f;
   int bi = BT_NONE, wi = -1;
@@ -143,23 +186,29 @@ extern "C" long rv_beam_topk_workspace_floats(int G, int K) {
   return (long)G * K * 2 * K * 2;                       // per row 2K values, then per row 2K tokens
 }
 
-extern "C" int rv_beam_topk(const float* logits, long ldl, const float* score, int G, int K, int V_valid, float* cand_val,
-                            int* cand_parent, int* cand_tok, float* lse, float* workspace, long workspace_floats, void* stream) {
-  RV_REQUIRE(K >= 1 && K <= BT_MAXK, "rv_beam_topk: 1 <= K <= 8 beams");
-  RV_REQUIRE(G >= 1 && (long)G * K <= 65535, "rv_beam_topk: G >= 1, G * K <= 65535 rows");
-  RV_REQUIRE(V_valid <= BT_THREADS * 64, "rv_beam_topk: V_valid <= 65536 (the row is held in registers)");
-  RV_REQUIRE(V_valid >= 2 * K && ldl >= V_valid, "rv_beam_topk: V_valid >= 2 K candidates per row, ldl >= V_valid");
-  RV_REQUIRE(logits && score && cand_val && cand_parent && cand_tok && lse && workspace, "rv_beam_topk: NULL buffer");
-  RV_REQUIRE((((uintptr_t)logits | (uintptr_t)score | (uintptr_t)cand_val | (uintptr_t)cand_parent | (uintptr_t)cand_tok |
-               (uintptr_t)lse | (uintptr_t)workspace) & 3) == 0, "rv_beam_topk: buffers must be 4-byte aligned");
-  RV_REQUIRE(workspace_floats >= rv_beam_topk_workspace_floats(G, K),
-             "rv_beam_topk: workspace smaller than rv_beam_topk_workspace_floats(G, K)");
+// the checks and the two launches of rv_beam_topk and rv_beam_topk_penalty; pen.hist == nullptr = the plain kernel
+static int beam_topk_run(const char* who, const float* logits, long ldl, const float* score, int G, int K, int V_valid,
+                         const BeamPenalty pen, float* cand_val, int* cand_parent, int* cand_tok, float* lse, float* workspace,
+                         long workspace_floats, void* stream) {
+  RV_REQUIRE_AS(who, K >= 1 && K <= BT_MAXK, "1 <= K <= 8 beams");
+  RV_REQUIRE_AS(who, G >= 1 && (long)G * K <= 65535, "G >= 1, G * K <= 65535 rows");
+  RV_REQUIRE_AS(who, V_valid <= BT_THREADS * 64, "V_valid <= 65536 (the row is held in registers)");
+  RV_REQUIRE_AS(who, V_valid >= 2 * K && ldl >= V_valid, "V_valid >= 2 K candidates per row, ldl >= V_valid");
+  RV_REQUIRE_AS(who, logits && score && cand_val && cand_parent && cand_tok && lse && workspace, "NULL buffer");
+  RV_REQUIRE_AS(who, (((uintptr_t)logits | (uintptr_t)score | (uintptr_t)cand_val | (uintptr_t)cand_parent | (uintptr_t)cand_tok |
+                       (uintptr_t)lse | (uintptr_t)workspace) & 3) == 0, "buffers must be 4-byte aligned");
+  RV_REQUIRE_AS(who, workspace_floats >= rv_beam_topk_workspace_floats(G, K),
+                "workspace smaller than rv_beam_topk_workspace_floats(G, K)");
   const int M = G * K, n = 2 * K;
   float* row_val = workspace;
   int* row_tok = (int*)(workspace + (long)M * n);
   const int vec = (((uintptr_t)logits & 15) == 0 && ldl % 4 == 0) ? 1 : 0;
-#define BT_LAUNCH(IPT)                                                                                                   \
-  launch<beam_topk_row_kernel<IPT>>(0, dim3(M), dim3(BT_THREADS), stream, logits, ldl, V_valid, score, vec, n, row_val, row_tok, lse)
+  const int lds = pen.hist ? ((V_valid + 31) >> 5) * 4 : 0;
+#define BT_LAUNCH(IPT)                                                                                                          \
+  (pen.hist ? launch<beam_topk_row_kernel<IPT, true>>(lds, dim3(M), dim3(BT_THREADS), stream, logits, ldl, V_valid, score, vec, n, \
+                                                      row_val, row_tok, lse, pen)                                               \
+            : launch<beam_topk_row_kernel<IPT, false>>(0, dim3(M), dim3(BT_THREADS), stream, logits, ldl, V_valid, score, vec, n, \
+                                                       row_val, row_tok, lse, pen))
   int rc;
   if (V_valid <= BT_THREADS * 8) rc = BT_LAUNCH(8);
   else if (V_valid <= BT_THREADS * 32) rc = BT_LAUNCH(32);
@@ -168,6 +217,27 @@ extern "C" int rv_beam_topk(const float* logits, long ldl, const float* score, i
   if (rc) return rc;
   return launch<beam_topk_merge_kernel>(0, dim3(G), dim3(64), stream, (const float*)row_val, (const int*)row_tok, K, V_valid, n,
                                         cand_val, cand_parent, cand_tok);
+}
+
+extern "C" int rv_beam_topk(const float* logits, long ldl, const float* score, int G, int K, int V_valid, float* cand_val,
+                            int* cand_parent, int* cand_tok, float* lse, float* workspace, long workspace_floats, void* stream) {
+  return beam_topk_run("rv_beam_topk", logits, ldl, score, G, K, V_valid, BeamPenalty{nullptr, 0, 0, 1.f}, cand_val, cand_parent,
+                       cand_tok, lse, workspace, workspace_floats, stream);
+}
+
+extern "C" int rv_beam_topk_penalty(const float* logits, long ldl, const float* score, int G, int K, int V_valid, const int* hist,
+                                    long ld_h, int n_hist, float penalty, float* cand_val, int* cand_parent, int* cand_tok,
+                                    float* lse, float* workspace, long workspace_floats, void* stream) {
+  const char* who = "rv_beam_topk_penalty";
+  RV_REQUIRE_AS(who, penalty > 0.f, "penalty must be > 0 (1 = off)");               // false for a NaN as well
+  RV_REQUIRE_AS(who, n_hist >= 0 && n_hist <= ld_h, "0 <= n_hist <= ld_h (the row length of the history table)");
+  RV_REQUIRE_AS(who, hist != nullptr || n_hist == 0 || penalty == 1.f, "hist is NULL with n_hist > 0 and penalty != 1");
+  RV_REQUIRE_AS(who, ((uintptr_t)hist & 3) == 0, "hist must be 4-byte aligned");
+  RV_REQUIRE_AS(who, G < 1 || K < 1 || ld_h <= 0x7fffffffL / ((long)G * K), "G * K * ld_h must fit int32");
+  const bool on = hist != nullptr && n_hist > 0 && penalty != 1.f;                  // else: rv_beam_topk's kernel, its bits
+  const BeamPenalty pen = on ? BeamPenalty{hist, ld_h, n_hist, penalty} : BeamPenalty{nullptr, 0, 0, 1.f};
+  return beam_topk_run(who, logits, ldl, score, G, K, V_valid, pen, cand_val, cand_parent, cand_tok, lse, workspace,
+                       workspace_floats, stream);
 }
 
 // ------------------------------------------------------------------ one beam step

@@ -1217,7 +1217,8 @@ class LlavaDPOModel:
         cfg, st = self.cfg, self.store
         if self.lora is not None:
             raise NotImplementedError("generate(): un-merged LoRA adapters are not supported - merge_lora() first")
-        if getattr(cfg, "arch", "llava") == "omnilmm" or self._row_splicer() is not None:
+        if not getattr(self, "_decodes_spliced_rows", False) and (getattr(cfg, "arch", "llava") == "omnilmm"
+                                                                  or self._row_splicer() is not None):
             raise NotImplementedError("generate(): OmniLMM (resampler splice) is not supported")
         if num_beams != 1:
             raise NotImplementedError("generate(): beam search (num_beams > 1) is not supported here - use beam_search()")
@@ -1245,7 +1246,7 @@ class LlavaDPOModel:
         T, dev = int(max_new_tokens), self.device
         with self._eval_mode():
             cpu_plan = build_branch_plan([[p] for p in prompts], cfg.n_image_tokens, cfg.model_max_length,
-                                         splicer=None, pad_free=True, packed=False)
+                                         splicer=self._row_splicer(), pad_free=True, packed=False)
             rows = plan_decode_rows(cpu_plan.row_off.tolist(), cpu_plan.row_len.tolist(), repeat, T)
             M = rows.n_seq
             self._rope(cpu_plan.L + T)
@@ -1335,12 +1336,14 @@ class LlavaDPOModel:
         Test hooks, keyword-only: ``_uniforms`` (callable index -> fp32 [max_new_tokens, repeat]) replaces the table;
         ``_scores`` (callable (index, sample, step, fp32 logits [vocab])) sees every row a live slot is sampled from (rows
         behind a sequence's end included, until the poll that frees the slot); ``_scheduler`` (a list) receives the
-        SlotScheduler.  Refused by name before anything is launched: OmniLMM, un-merged LoRA, head_dim != 128,
+        SlotScheduler.  Refused by name before anything is launched: a row splicer the class does not decode with
+        (``_decodes_spliced_rows``; OmniLMMDPOModel sets it), un-merged LoRA, head_dim != 128,
         num_beams != 1, repeat > slots; a prompt longer than ``max_prompt_tokens`` when its request is reached."""
         cfg = self.cfg
         if self.lora is not None:
             raise NotImplementedError("generate_continuous(): un-merged LoRA adapters are not supported - merge_lora() first")
-        if getattr(cfg, "arch", "llava") == "omnilmm" or self._row_splicer() is not None:
+        if not getattr(self, "_decodes_spliced_rows", False) and (getattr(cfg, "arch", "llava") == "omnilmm"
+                                                                  or self._row_splicer() is not None):
             raise NotImplementedError("generate_continuous(): OmniLMM (resampler splice) is not supported")
         if num_beams != 1:
             raise NotImplementedError("generate_continuous(): beam search (num_beams > 1) is not supported - use beam_search()")
@@ -1422,8 +1425,8 @@ class LlavaDPOModel:
                     if not batch:
                         break
                     prompts = [b[1] for b in batch]
-                    cpu_plan = build_branch_plan([[p] for p in prompts], cfg.n_image_tokens, cfg.model_max_length, splicer=None,
-                                                 pad_free=True, packed=False)
+                    cpu_plan = build_branch_plan([[p] for p in prompts], cfg.n_image_tokens, cfg.model_max_length,
+                                                 splicer=self._row_splicer(), pad_free=True, packed=False)
                     lens = cpu_plan.row_len.tolist()
                     for (index, _, _, _), n in zip(batch, lens):
                         if n > max_prompt:
@@ -1495,7 +1498,7 @@ class LlavaDPOModel:
 
     # ------------------------------------------------------------------ beam-search decoding (the evaluation stage)
     def beam_search(self, prompts, images, max_new_tokens: int, num_beams: int = 3, eos_token_id: Optional[int] = None,
-                    length_penalty: float = 1.0, return_trace: bool = False, *, _forced=None):
+                    length_penalty: float = 1.0, return_trace: bool = False, repetition_penalty: float = 1.0, *, _forced=None):
         """One answer per (image, prompt) the way the reference's evaluation produces it (muffin/eval/muffin_vqa.py,
         llava15_chair.py, chat.py: ``generate(do_sample=False, num_beams=3, max_new_tokens=)`` from inputs_embeds): HF's
         GenerationMixin._beam_search with early_stopping=False and one EOS id.  Prefill is ``generate``'s (_prefill); its
@@ -1508,6 +1511,10 @@ class LlavaDPOModel:
         its rows and is decoded on until all are (its finished set is frozen), as in ``generate``.
         Returns (tokens, scores): tokens[k] = the new token ids of prompt k's best hypothesis (it ends with ``eos_token_id`` if
         it finished on it), scores[k] = its ``sequences_scores`` = sum of log-probs / length ** length_penalty.
+        ``repetition_penalty`` != 1 (omnilmm/omnilmm_gen_data.py:306-314): HF's RepetitionPenaltyLogitsProcessor where beam search
+        runs it, on the log-softmax before the beam score is added, over the tokens the beam has GENERATED (its row of the token
+        history; no prompt id, as in ``generate``) - rv_beam_topk_penalty.  The summed scores are then sums of penalised
+        log-probs, as HF's are.  1.0 = rv_beam_topk, today's bits.
         ``return_trace`` (tests): a third value, a dict of per-step tensors - ``logits`` [steps, M, vocab] fp32, the device's
         candidates ``cand_val`` / ``cand_parent`` / ``cand_tok`` [steps, G, 2K], its running beams ``parent`` / ``token`` /
         ``score`` [steps, M], and ``done`` [steps, G], ``n_hyp`` [steps, G], ``hyp_score`` / ``hyp_len`` [steps, G, K] after each
@@ -1517,7 +1524,8 @@ class LlavaDPOModel:
         cfg = self.cfg
         if self.lora is not None:
             raise NotImplementedError("beam_search(): un-merged LoRA adapters are not supported - merge_lora() first")
-        if getattr(cfg, "arch", "llava") == "omnilmm" or self._row_splicer() is not None:
+        if not getattr(self, "_decodes_spliced_rows", False) and (getattr(cfg, "arch", "llava") == "omnilmm"
+                                                                  or self._row_splicer() is not None):
             raise NotImplementedError("beam_search(): OmniLMM (resampler splice) is not supported")
         if cfg.head_dim != 128:
             raise NotImplementedError("beam_search(): rv_attn_decode_indexed needs head_dim 128")
@@ -1527,11 +1535,13 @@ class LlavaDPOModel:
             raise ValueError(f"{len(prompts)} prompts for {len(images)} images")
         if max_new_tokens < 1:
             raise ValueError("beam_search(): max_new_tokens must be >= 1")
+        if not repetition_penalty > 0:
+            raise ValueError("beam_search(): repetition_penalty must be > 0 (1.0 = off)")
         from .splice import plan_beam_rows
         T, K, G, dev = int(max_new_tokens), int(num_beams), len(prompts), self.device
         with self._eval_mode():
             cpu_plan = build_branch_plan([[p] for p in prompts], cfg.n_image_tokens, cfg.model_max_length,
-                                         splicer=None, pad_free=True, packed=False)
+                                         splicer=self._row_splicer(), pad_free=True, packed=False)
             rows = plan_beam_rows(cpu_plan.row_off.tolist(), cpu_plan.row_len.tolist(), K, T)
             M = rows.n_seq
             self._rope(cpu_plan.L + T)
@@ -1562,7 +1572,11 @@ class LlavaDPOModel:
                         self._decode_step(state.token[c0:c1], pos[c0:c1], dst[c0:c1], (pre_off[c0:c1], rows.pre_len[c0:c1],
                                           own_len[c0:c1]), caches, n_split, logits[c0:c1], own_rows=state.own_rows[c0:c1],
                                           cur_own_len=j)
-                cand = ops.beam_topk(logits, state.run_score, G, K, cfg.vocab)[:3]
+                if repetition_penalty != 1.0:
+                    cand = ops.beam_topk(logits, state.run_score, G, K, cfg.vocab, hist=state.hist, n_hist=j,
+                                         penalty=float(repetition_penalty))[:3]
+                else:
+                    cand = ops.beam_topk(logits, state.run_score, G, K, cfg.vocab)[:3]
                 ops.beam_step(state, cand, j, eos_token_id, length_penalty,
                               forced=None if forced is None else (forced[0][j], forced[1][j], forced[2][j]))
                 if return_trace:

@@ -69,6 +69,11 @@ class OmniLMMConfig(LlavaConfig):
 
 
 class OmniLMMDPOModel(LlavaDPOModel):
+    # generate / generate_continuous / beam_search plan their rows with _row_splicer(): the replacement splice keeps a prompt's
+    # length, the prefill is the training forward, the decode kernels take kv_group.  The base class refuses a splicer it was not
+    # told about by name; this attribute is the telling.
+    _decodes_spliced_rows = True
+
     def __init__(self, cfg: OmniLMMConfig, device="cuda:0", with_optimizer: bool = True, lora: Optional[LoraConfig] = None):
         if cfg.tune_clip:
             raise NotImplementedError("OmniLMMConfig.tune_clip=True (the tower as a trained submodule, omnilmm/model/omnilmm.py:58,"

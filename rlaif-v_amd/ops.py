@@ -984,10 +984,14 @@ def attn_decode_indexed(q: torch.Tensor, kv: torch.Tensor, H: int, hd: int, k_co
     return out, lse
 
 
-def beam_topk(logits: torch.Tensor, score: torch.Tensor, n_groups: int, num_beams: int, v_valid: int):
+def beam_topk(logits: torch.Tensor, score: torch.Tensor, n_groups: int, num_beams: int, v_valid: int,
+              hist: Optional[torch.Tensor] = None, n_hist: int = 0, penalty: float = 1.0):
     """Per group of ``num_beams`` rows of fp32 ``logits`` [>= G K, ld] the 2K best of log_softmax(row)[v] + score[row] over the
     columns [0, v_valid), sorted descending, equal values by the lower beam * v_valid + v (rv_beam_topk).
-    Returns (value fp32, parent int32, token int32: [G, 2K] each; lse fp32 [G K])."""
+    ``hist`` (int32 [>= G K, ld_h], unit column stride), ``n_hist``, ``penalty``: HF's repetition penalty on the log-softmax,
+    before the score is added, once for every distinct id among the first ``n_hist`` entries of the row's history
+    (rv_beam_topk_penalty; ``BeamState.hist`` at step j with n_hist = j).  Without ``hist`` the call is rv_beam_topk's.
+    Returns (value fp32, parent int32, token int32: [G, 2K] each; lse fp32 [G K], un-penalised)."""
     G, K = int(n_groups), int(num_beams)
     if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1 or not logits.is_cuda:
         raise ValueError("beam_topk: logits must be a 2-D fp32 CUDA tensor with unit column stride")
@@ -998,12 +1002,26 @@ def beam_topk(logits: torch.Tensor, score: torch.Tensor, n_groups: int, num_beam
     dev = logits.device
     if score.dtype != torch.float32 or score.numel() != G * K or not score.is_contiguous() or score.device != dev:
         raise ValueError(f"beam_topk: score must be contiguous fp32 [{G * K}] on the logits' device")
+    if hist is None:
+        if n_hist != 0 or penalty != 1.0:
+            raise ValueError("beam_topk: n_hist and penalty need hist (the token-history table)")
+    else:
+        if hist.dim() != 2 or hist.dtype != torch.int32 or hist.stride(1) != 1 or hist.device != dev:
+            raise ValueError("beam_topk: hist must be a 2-D int32 tensor with unit column stride on the logits' device")
+        if not (hist.shape[0] >= G * K and 0 <= int(n_hist) <= hist.shape[1] and hist.stride(0) >= hist.shape[1]):
+            raise ValueError(f"beam_topk: {G * K} rows of {n_hist} ids do not fit hist {tuple(hist.shape)}")
+        if not float(penalty) > 0.0:
+            raise ValueError(f"beam_topk: penalty must be > 0 (1 = off), got {penalty}")
     val = torch.empty(G, 2 * K, dtype=torch.float32, device=dev)
     par = torch.empty(G, 2 * K, dtype=torch.int32, device=dev)
     tok = torch.empty(G, 2 * K, dtype=torch.int32, device=dev)
     lse = torch.empty(G * K, dtype=torch.float32, device=dev)
     ws = torch.empty(int(hip.lib().lib.rv_beam_topk_workspace_floats(G, K)), dtype=torch.float32, device=dev)
-    hip.call("rv_beam_topk", logits, logits.stride(0), score, G, K, int(v_valid), val, par, tok, lse, ws, ws.numel())
+    if hist is None:
+        hip.call("rv_beam_topk", logits, logits.stride(0), score, G, K, int(v_valid), val, par, tok, lse, ws, ws.numel())
+        return val, par, tok, lse
+    hip.call("rv_beam_topk_penalty", logits, logits.stride(0), score, G, K, int(v_valid), hist, hist.stride(0), int(n_hist),
+             float(penalty), val, par, tok, lse, ws, ws.numel())
     return val, par, tok, lse
 
 
